@@ -22,7 +22,14 @@ call over all N GPUs and the other ranks only join the CPU (gloo) barriers
 around the timed region.  `--mode dist` keeps the one-process-per-GPU layout
 (RCCL all-gather of the sketches, galah_amd/sharding.py) for comparison.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5]
+A plain run (`--gpus 1 --steps K --warmup W`) only sets up, warms up, times
+the K steps and prints the result line.  Everything else the benchmark
+measures -- the rooflines (K1's needs a disassembly of the library, K2's a
+sketch run and a pass over the sketches), the CPU baseline, the downstream
+partition, the files legs and the C4 leg -- runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step returned as .npy files.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -83,21 +90,31 @@ def parse():
     ap.add_argument("--devices", default=None,
                     help="lib mode: comma-separated HIP ordinals (repeats allowed, e.g. 0,0 to run the sharded "
                          "path on one GPU); default: 0..gpus-1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures: rooflines, CPU "
+                         "baseline, downstream partition, files legs, C4 leg (the options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the passing pairs' i, j, common, total and their "
+                         "f32 ANI) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--files", dest="files", action="store_true", default=None,
                     help="add the ingest-inclusive leg (C2's genomes as gzip FASTA files through "
-                         "gg_precluster_files); on by default for the one-GPU C3 headline")
+                         "gg_precluster_files); on by default for the one-GPU C3 headline with --full")
     ap.add_argument("--no-files", dest="files", action="store_false")
     ap.add_argument("--files-genomes", type=int, default=1000, help="genomes in the files leg (C2: 1000)")
     ap.add_argument("--c4", dest="c4_leg", action="store_true", default=None,
                     help="add the north-star leg (C4: 100k x 3 Mbp, s=1000 on one GPU, 3 steps); on by default for "
-                         "the one-GPU C3 headline")
+                         "the one-GPU C3 headline with --full")
     ap.add_argument("--no-c4", dest="c4_leg", action="store_false")
     ap.add_argument("--c4-steps", type=int, default=3)
     ap.add_argument("--cpu-budget-s", type=float, default=24.0)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="dist mode: gloo stages collectives through host memory (ranks sharing one GPU)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full and (a.files or a.c4_leg):
+        ap.error("--files and --c4 are legs of the full run: add --full")
     if a.genomes is None:
         a.genomes = {"c2": 1000, "c4": 100000}.get(a.config, 10000)
     if a.sketch is None:
@@ -119,6 +136,27 @@ def make_shard(ctx, a, g0, g1, dev):
     d_words = torch.empty(max(1, n * a.genome_len // 16), dtype=torch.int32, device="cuda:%d" % dev)
     runs = ctx.synth_device(n, a.genome_len, a.cluster, a.max_sub, a.seed, d_words, first_genome=g0)
     return d_words, runs, n * a.genome_len
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: 1-D or 2-D array} as out_dir/<name>.npy (float32 stays
+    float32, everything else becomes float64: the integers here are far
+    below 2^53).  All arrays have one row per passing pair; past 64 MB in
+    all, the same fixed, seeded sample of rows is kept of each."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=(np.float32 if v.dtype == np.float32 else np.float64))
+              for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    per_row = sum(v.dtype.itemsize * (v.size // max(1, rows)) for v in arrays.values())
+    keep = (DUMP_MAX_BYTES - 4096 * len(arrays)) // max(1, per_row)
+    if rows > keep:
+        sel = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {k: v[sel] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def sync_all(devs):
@@ -834,10 +872,14 @@ def run_lib(a, world, rank):
         ms_step = elapsed_max / a.steps * 1e3
         npairs = N * (N - 1) // 2
         note = ("per-launch figures are device 0's (%d of %d genomes)" % (shards[0][2], N)) if M > 1 else ""
-        roof = roofline(kst["sketch"], kst["pairs"], s, note)
+        if a.dump_outputs:  # what the last timed precluster_shards call returned
+            dump_outputs(a.dump_outputs, {"pairs_i": pairs["i"], "pairs_j": pairs["j"],
+                                          "pairs_common": pairs["common"], "pairs_total": pairs["total"],
+                                          "ani": np.asarray(ani, dtype=np.float32)})
+        roof = roofline(kst["sketch"], kst["pairs"], s, note) if a.full else None
         pmc_config = a.config if M == 1 and N == {"c3": 10000, "c5": 10000}.get(a.config) else None
         downstream = None
-        if M == 1 and found:
+        if a.full and M == 1 and found:
             t1 = time.perf_counter()
             members, offsets = ga.partition_preclusters(N, pairs)
             t_part = time.perf_counter() - t1
@@ -850,7 +892,7 @@ def run_lib(a, world, rank):
         cpu = None
         roof_k2 = None
         d_sk = d_len = None
-        if M == 1:  # the step's sketches, for K2's byte model and the CPU baseline's parity spot check
+        if a.full and M == 1:  # the step's sketches, for K2's byte model and the CPU baseline's parity spot check
             d_words, runs, _ = shards[0]
             d_sk = torch.zeros((N, s), dtype=torch.int64, device="cuda:%d" % devs[0])
             d_len = torch.zeros(N, dtype=torch.int32, device="cuda:%d" % devs[0])
@@ -859,7 +901,7 @@ def run_lib(a, world, rank):
             kp = dict(kst["pairs"])
             kp["launches_sets"] = kst["pairs"]["launches"]
             roof_k2 = roofline_k2(k2_algorithmic_bytes(d_sk, d_len, N, s), kp, pmc_config)
-        if world == 1 and M == 1 and not a.no_cpu_baseline and a.config in ("c2", "c3", "c4"):
+        if a.full and world == 1 and M == 1 and not a.no_cpu_baseline and a.config in ("c2", "c3", "c4"):
             n_sample = cpu_threads()
             sample = d_words[: n_sample * a.genome_len // 16].cpu().numpy().view(np.uint32)
             cpu = cpu_baseline(sample, a.genome_len, d_sk.cpu().numpy().view(np.uint64),
@@ -876,13 +918,13 @@ def run_lib(a, world, rank):
         del shards, keep, d_words, runs
         torch.cuda.empty_cache()
         files = files_plain = c4 = None
-        want_files = a.files if a.files is not None else (a.config == "c3")
+        want_files = a.full and (a.files if a.files is not None else (a.config == "c3"))
         if world == 1 and M == 1 and want_files:
             try:
                 files, files_plain = files_leg(a, devs[0], 9)
             except Exception as e:  # the headline stands without it
                 files = {"error": "%s: %s" % (type(e).__name__, e)}
-        want_c4 = a.c4_leg if a.c4_leg is not None else (a.config == "c3")
+        want_c4 = a.full and (a.c4_leg if a.c4_leg is not None else (a.config == "c3"))
         if world == 1 and M == 1 and want_c4:
             try:
                 c4 = c4_leg(a, devs[0])
@@ -907,14 +949,18 @@ def run_lib(a, world, rank):
             "pairs_found": found,
             "pair_paths": pair_paths,
             "fallbacks": fallbacks,
-            "roofline": roof,
-            "roofline_k2": roof_k2,
-            "cpu_baseline": cpu,
-            "downstream": downstream,
-            "files": files,
-            "files_plain": files_plain,
-            "c4_one_gpu": c4,
+            "full": a.full,
         }
+        if a.full:
+            line.update({
+                "roofline": roof,
+                "roofline_k2": roof_k2,
+                "cpu_baseline": cpu,
+                "downstream": downstream,
+                "files": files,
+                "files_plain": files_plain,
+                "c4_one_gpu": c4,
+            })
     if world > 1:
         dist.destroy_process_group()
     return line
@@ -982,7 +1028,7 @@ def run_dist(a, world, rank, local):
     t0 = time.perf_counter()
     found = 0
     for _ in range(a.steps):
-        found, _h = step()
+        found, last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -991,6 +1037,9 @@ def run_dist(a, world, rank, local):
            (("sketch", ga.KERNEL_SKETCH), ("pairs", ga.KERNEL_PAIRS), ("index", ga.KERNEL_PAIRS_INDEX))}
     kst["pairs"]["ms"] += kst["index"]["ms"]
     ctx.timing_enable(False)
+    if a.dump_outputs:  # this rank's passing (i, j, common, total) rows of the last timed step, sorted
+        rows = last.numpy().reshape(-1, 4)
+        dump_outputs(a.dump_outputs, {"pairs_rank%d" % rank: rows[np.lexsort(rows.T[::-1])]})
     t = torch.tensor([elapsed, float(found), float(bases_loc)], dtype=torch.float64,
                      device="cpu" if gloo else "cuda")
     tmax, tsum = t.clone(), t.clone()
@@ -1011,9 +1060,11 @@ def run_dist(a, world, rank, local):
                        "sketch_size": s, "k": a.k, "min_ani": float(min_ani), "parallelism": "dp%d" % world,
                        "mode": "dist"},
             "pairs_found": int(tsum[1]),
-            "roofline": roofline(kst["sketch"], kst["pairs"], s, "rank 0's launches"),
-            "cpu_baseline": None,
+            "full": a.full,
         }
+        if a.full:
+            line.update({"roofline": roofline(kst["sketch"], kst["pairs"], s, "rank 0's launches"),
+                         "cpu_baseline": None})
     ctx.close()
     if world > 1:
         dist.destroy_process_group()

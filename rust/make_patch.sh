@@ -17,6 +17,7 @@ trap 'rm -rf "$t"' EXIT
 mkdir -p "$t/a/src" "$t/b/src"
 for f in Cargo.toml src/lib.rs src/finch.rs; do cp "$ref/$f" "$t/a/$f"; cp "$ref/$f" "$t/b/$f"; done
 cp "$here/galah/src/finch_gpu.rs" "$t/b/src/finch_gpu.rs"
+chmod -R u+w "$t"  # (a read-only reference tree gives read-only copies)
 python3 - "$t/b" <<'PY'
 import sys
 b = sys.argv[1]

@@ -256,6 +256,64 @@ def test_patch_carries_the_body():
     assert "return crate::finch_gpu::distances(genome_fasta_paths, min_ani, num_kmers, kmer_length);" in patch
 
 
+def _patch_hunks(patch):
+    """{path: [(old_start, new_start, old_lines, new_lines)]} of a unified diff."""
+    files, cur = {}, None
+    for line in patch.splitlines():
+        if line.startswith("+++ "):
+            cur = files.setdefault(line[4:].strip()[2:], [])
+        elif line.startswith(("diff ", "--- ")):
+            continue
+        elif line.startswith("@@"):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            cur.append([int(m.group(1)), int(m.group(3)), [], [],
+                        int(m.group(2) or 1), int(m.group(4) or 1)])
+        elif cur:
+            if line[:1] in (" ", "-"):
+                cur[-1][2].append(line[1:])
+            if line[:1] in (" ", "+"):
+                cur[-1][3].append(line[1:])
+    for hunks in files.values():
+        for h in hunks:
+            assert len(h[2]) == h[4] and len(h[3]) == h[5], "hunk header and body disagree"
+    return {p: [tuple(h[:4]) for h in hs] for p, hs in files.items()}
+
+
+def test_patch_applies_to_its_own_base_without_fuzz():
+    """Needs no galah tree: every file the patch changes is rebuilt from the
+    hunks' own context and removed lines at the line numbers their headers
+    give (blank lines between them), `patch --fuzz=0` applies there, and
+    each hunk's new side lands where its header says."""
+    patch = open(PATCH).read()
+    files = _patch_hunks(patch)
+    assert sorted(files) == ["Cargo.toml", "src/finch.rs", "src/finch_gpu.rs", "src/lib.rs"]
+    d = tempfile.mkdtemp()
+    try:
+        os.makedirs(os.path.join(d, "src"))
+        base_len = {}
+        for path, hunks in files.items():
+            if hunks[0][0] == 0:  # a new file
+                assert path == "src/finch_gpu.rs" and len(hunks) == 1
+                continue
+            lines = [""] * max(s - 1 + len(old) for s, _, old, _ in hunks)
+            for s, _, old, _ in hunks:
+                lines[s - 1:s - 1 + len(old)] = old
+            base_len[path] = len(lines)
+            open(os.path.join(d, path), "w").write("\n".join(lines) + "\n")
+        r = subprocess.run(["patch", "-p1", "--fuzz=0", "-i", PATCH], cwd=d, capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert "offset" not in r.stdout and "fuzz" not in r.stdout, r.stdout
+        for path, hunks in files.items():
+            got = open(os.path.join(d, path)).read().split("\n")[:-1]
+            for _, s, _, new in hunks:
+                assert got[s - 1:s - 1 + len(new)] == new, (path, s)
+            if path in base_len:
+                assert len(got) == base_len[path] + sum(len(new) - len(old) for _, _, old, new in hunks)
+        assert open(os.path.join(d, "src", "finch_gpu.rs")).read() == open(BODY).read()
+    finally:
+        shutil.rmtree(d)
+
+
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "src")), reason="reference tree not present")
 def test_patch_is_current_and_applies_to_the_reference():
     d = tempfile.mkdtemp()
