@@ -880,10 +880,12 @@ gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, u
   // them into b.cost: per entry of a shared hash, the other sketches holding
   // it); the gate kernel's, the pair count x s.  Clusters of thousands of
   // near-identical genomes make the first grow as g^2 per hash (C3 with
-  // clusters of 1,000: 2.7e9 reads, index 25 ms against ~3 ms of gate), so
-  // past kIndexCost x s x pairs member reads the pairs kernel emits nothing
-  // and the gate kernel runs instead (GALAHGPU_INDEX_COST=<factor>, 0: never;
-  // never either when the index is asked for by GALAHGPU_PAIRS_KERNEL=index)
+  // clusters of 1,000: 2.7e9 reads, index 25 ms against ~3 ms of gate).
+  // The fallback that weighs the two is off by default: with
+  // GALAHGPU_INDEX_COST=<factor> set to a positive number, past
+  // factor x s x pairs member reads the pairs kernel emits nothing and the
+  // gate kernel runs instead (unset, empty or 0: never; never either when
+  // the index is asked for by GALAHGPU_PAIRS_KERNEL=index)
   {
     const char* e = getenv("GALAHGPU_INDEX_COST");
     const double k = !weigh_cost ? 0.0 : e && *e ? atof(e) : 0.0;
