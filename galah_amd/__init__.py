@@ -9,6 +9,7 @@ of libgalahgpu.so (include/galahgpu.h):
   src/finch.rs:26-75   finch::distances                distances()
   src/sorted_pair_genome_distance_cache.rs:4-59        SortedPairGenomeDistanceCache
   src/cluster_argument_parsing.rs:1160-1182            parse_percentage()
+  src/genome_stats.rs:4-51                             GenomeAssemblyStats, calculate_genome_stats()
 
 There is no CPU fallback: importing works without a GPU (so the ABI can be
 inspected), but every compute call needs a gfx950 device and raises
@@ -29,6 +30,7 @@ __all__ = [
     "FinchPreclusterer", "distances", "PAIR_DTYPE", "LIB_PATH", "EXPORTED_SYMBOLS", "device_runs",
     "partition_preclusters", "precluster_pairs", "preclusters", "LOCAL_PAIR_DTYPE",
     "sketch_cache_load", "sketch_cache_store",
+    "GenomeAssemblyStats", "calculate_genome_stats", "genome_stats", "STATS_DTYPE",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -51,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "gg_sketch_cache_load", "gg_sketch_cache_store", "gg_sketch_files", "gg_precluster_files_cached",
     "gg_create_multi", "gg_device_count", "gg_device_ctx", "gg_set_host_threads", "gg_phase_times",
     "gg_precluster_shards", "gg_fallbacks", "gg_peer_links", "gg_info_line", "gg_precluster_files_each",
+    "gg_genome_stats_files", "gg_sketch_files_stats",
 )
 
 GG_OK = 0
@@ -144,6 +147,8 @@ _sig("gg_precluster_files_each", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u
                                         ctypes.POINTER(_u64), ctypes.POINTER(_u32)])
 _sig("gg_sketch_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp,
                                ctypes.POINTER(_u32)])
+_sig("gg_genome_stats_files", _i32, [ctypes.POINTER(ctypes.c_char_p), _u32, _i32, _vp])
+_sig("gg_sketch_files_stats", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp, _vp])
 _sig("gg_sketch_cache_load", _i32, [ctypes.c_char_p, ctypes.c_char_p, _i32, _u32, _u64, _vp,
                                     ctypes.POINTER(_u32), ctypes.POINTER(_i32)])
 _sig("gg_sketch_cache_store", _i32, [ctypes.c_char_p, ctypes.c_char_p, _i32, _u32, _u64, _vp, _u32])
@@ -306,6 +311,62 @@ def sketch_cache_store(cache_dir, path, hashes, k=21, s=1000, seed=0):
                                   _ptr(h), len(h))
     if st != GG_OK:
         raise _thread_err(st)
+
+
+# gg_genome_stats
+STATS_DTYPE = np.dtype([("num_contigs", np.uint64), ("num_ambiguous_bases", np.uint64), ("n50", np.uint64),
+                        ("total_bases", np.uint64)])
+
+
+class GenomeAssemblyStats:
+    """src/genome_stats.rs:4-9: num_contigs, num_ambiguous_bases, n50
+    (#[derive(Debug, PartialEq)] over those three).  total_bases, which the
+    reference computes and drops, rides along outside equality and repr."""
+
+    __slots__ = ("num_contigs", "num_ambiguous_bases", "n50", "total_bases")
+
+    def __init__(self, num_contigs, num_ambiguous_bases, n50, total_bases=None):
+        self.num_contigs = int(num_contigs)
+        self.num_ambiguous_bases = int(num_ambiguous_bases)
+        self.n50 = int(n50)
+        self.total_bases = None if total_bases is None else int(total_bases)
+
+    def _key(self):
+        return (self.num_contigs, self.num_ambiguous_bases, self.n50)
+
+    def __eq__(self, other):
+        if not isinstance(other, GenomeAssemblyStats):
+            return NotImplemented
+        return self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "GenomeAssemblyStats { num_contigs: %d, num_ambiguous_bases: %d, n50: %d }" % self._key()
+
+
+def _stats_list(arr):
+    return [GenomeAssemblyStats(int(r["num_contigs"]), int(r["num_ambiguous_bases"]), int(r["n50"]),
+                                int(r["total_bases"])) for r in arr]
+
+
+def genome_stats(paths, threads=0):
+    """src/genome_stats.rs:11 for every file, on `threads` host threads (0:
+    the default of pack_files) -> a list of GenomeAssemblyStats.  Host only."""
+    n = len(paths)
+    arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+    out = np.zeros(max(n, 1), dtype=STATS_DTYPE)
+    st = _L.gg_genome_stats_files(arr, n, int(threads), _ptr(out))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return _stats_list(out[:n])
+
+
+def calculate_genome_stats(fasta_path):
+    """src/genome_stats.rs:11-51 (a file that does not read or parse raises,
+    where the reference panics)."""
+    return genome_stats([fasta_path], threads=1)[0]
 
 
 class Packed:
@@ -605,6 +666,22 @@ class Context:
         if st != GG_OK:
             raise self._err(st)
         return out[:n], lens[:n], hits.value
+
+    def sketch_files_stats(self, paths, cache_dir=None):
+        """sketch_files plus every genome's GenomeAssemblyStats from the same
+        read of each file (gg_sketch_files_stats) -> (sketches, lens, stats).
+        cache_dir is written, never read: a later precluster_files over the
+        same files, in any order, finds every sketch there."""
+        n = len(paths)
+        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        out = np.zeros((max(n, 1), self.s), dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        stats = np.zeros(max(n, 1), dtype=STATS_DTYPE)
+        st = _L.gg_sketch_files_stats(self._c, arr, n, None if cache_dir is None else os.fsencode(cache_dir),
+                                      _ptr(out), _ptr(lens), _ptr(stats))
+        if st != GG_OK:
+            raise self._err(st)
+        return out[:n], lens[:n], _stats_list(stats[:n])
 
     def precluster_files(self, paths, min_ani, cache_dir=None):
         """-> (pairs structured array sorted by (i, j), ani f32 array).  With

@@ -250,9 +250,12 @@ gg_status inflate_batch(gg_ctx* m, const uint8_t* h_in, uint64_t in_bytes, const
 // One batch of FASTA text already in device memory (d_text, file f at
 // foff[f]) parsed on the device: 2-bit words into *d_words (scratch of m),
 // runs of >= k bases (genome = file index in the batch) into runs.
-// Synchronises m->stream.  (multi.cpp)
+// Synchronises m->stream.  stats (optional): the files' assembly statistics
+// (src/genome_stats.rs:11-51) from two more passes over the same text; not
+// asked for, the call launches the parser's three kernels only.  (multi.cpp)
 gg_status parse_raw_batch(gg_ctx* m, const uint8_t* d_text, const std::vector<uint64_t>& foff, uint32_t** d_words,
-                          uint64_t* n_words, std::vector<gg_run>& runs);
+                          uint64_t* n_words, std::vector<gg_run>& runs,
+                          std::vector<gg_genome_stats>* stats = nullptr);
 
 // A timing event of c (a spare one, else a new one; nullptr on failure).
 hipEvent_t take_event(gg_ctx* c);
@@ -289,6 +292,7 @@ struct GzClaims {
   const uint32_t* row_of = nullptr;    // their rows in the call's sketch array
   uint32_t n = 0;
   const char* cache_dir = nullptr;     // new sketches stored there (files stamped before they are read)
+  gg_genome_stats* stats = nullptr;    // gg_sketch_files_stats: the files' statistics, by row (else null)
   std::mutex mu;
   uint32_t cursor = 0;
   std::vector<uint32_t> back;  // claimed, given back

@@ -210,6 +210,11 @@ hipError_t launch_pairs_gate(const GateLaunch& a, hipStream_t st);
 // parse.hip: one batch of raw FASTA text (files concatenated) -> 2-bit codes
 // and run starts; the host drives the passes and the per-block scans
 // (multi.cpp: parse_raw_batch).
+// pass 4, per block: the records it opens, its N / n among the sequence
+// bytes, and the sequence bytes before its first record start
+struct ParseStatsBlock {
+  uint32_t recs, amb, head, pad;
+};
 struct ParseLaunch {
   const uint8_t* raw;
   uint64_t n_bytes;
@@ -230,7 +235,16 @@ struct ParseLaunch {
   uint64_t* starts;      // pass 3 out (run start positions)
   uint64_t n_words;
   uint32_t* words;       // pass 3 out (cleared before)
+  // assembly statistics (passes 4 and 5, gg_sketch_files_stats only)
+  ParseStatsBlock* stats_blk = nullptr;  // pass 4 out
+  const uint64_t* rec_off = nullptr;    // [blocks] records opened before the block (in the batch)
+  const uint64_t* file_rec0 = nullptr;  // [files + 1] first record of each file
+  uint64_t n_recs = 0;
+  uint64_t* contig_len = nullptr;       // pass 5 out [n_recs] (cleared before)
+  const uint32_t* stats_list = nullptr; // pass 5's blocks: those that open a record
+  uint32_t n_stats_blocks = 0;
 };
+// passes 1-3: the parser; 4, 5: the statistics (after pass 1)
 hipError_t parse_batch_pass(int pass, const ParseLaunch& p, hipStream_t st);
 uint32_t parse_block_bytes();
 
@@ -494,8 +508,10 @@ class PackStream {
   // FASTA text for the device parser (parse.hip); FASTQ files are rewritten
   // as FASTA records on the way.  Otherwise they pack on the host.  (Gzip
   // lists for the device inflate are read by ingest_gz.cpp's stagers.)
+  // stats: the record walk also takes each genome's assembly statistics
+  // (stats(i); raw streams leave them to the device, parse.hip).
   PackStream(const char* const* paths, uint32_t n, int k, int n_threads, uint64_t budget_bytes,
-             bool stamp_files = false, bool raw = false);
+             bool stamp_files = false, bool raw = false, bool stats = false);
   ~PackStream();
   PackStream(const PackStream&) = delete;
   PackStream& operator=(const PackStream&) = delete;
@@ -508,6 +524,9 @@ class PackStream {
   // The file's size and mtime as stat'ed just before it was read (valid
   // after get(i) succeeded; the streams are built with stamp_files).
   FileStamp stamp(uint32_t i);
+  // Genome i's assembly statistics (streams built with stats; after get(i)
+  // succeeded, until release(i)).
+  gg_genome_stats stats(uint32_t i);
   void release(uint32_t i);
   void abort();
   // After an abort: joins the workers and returns the error of the lowest
@@ -525,6 +544,12 @@ class PackStream {
 // host fallback of the device inflate.  bytes may be consumed.
 gg_status host_text_from_bytes(std::vector<uint8_t>& bytes, const char* name, std::vector<uint8_t>& text,
                                std::string& err);
+
+// src/genome_stats.rs:33-50 from a genome's contig lengths (sorted in place)
+// and its N / n count: total_bases, and n50 as the reference's loop gives it
+// (ascending lengths, the first at which the running sum reaches total / 2;
+// 0 without a contig, where the reference panics).
+gg_genome_stats finish_genome_stats(uint64_t* contig_lens, uint64_t n_contigs, uint64_t n_ambiguous);
 
 // api.cpp helpers used by pack.cpp
 void set_thread_error(const std::string& msg);

@@ -459,7 +459,8 @@ class GzStager {
 // threads) and parses one staged batch on m's stream: 2-bit words into
 // *d_words, runs into runs.
 gg_status inflate_staged_batch(gg_ctx* m, GzStager& pipe, GzStaged& g, GzClaims& cl, int host_threads,
-                               uint32_t** d_words, uint64_t* nw, std::vector<gg_run>& runs) {
+                               uint32_t** d_words, uint64_t* nw, std::vector<gg_run>& runs,
+                               std::vector<gg_genome_stats>* stats) {
   const auto t0 = Clock::now();
   if (g.st != GG_OK) return fail(m, g.st, g.err);
   if (g.file_err) {  // (the call reports the file's own error; the batch's other files were never decoded)
@@ -524,7 +525,7 @@ gg_status inflate_staged_batch(gg_ctx* m, GzStager& pipe, GzStaged& g, GzClaims&
     if (foff[nf]) GG_HIP(m, hipMemcpyAsync(d_text, all.data(), foff[nf], hipMemcpyHostToDevice, m->stream));
     GG_HIP(m, hipStreamSynchronize(m->stream));
   }
-  const gg_status ps = parse_raw_batch(m, d_text, foff, d_words, nw, runs);
+  const gg_status ps = parse_raw_batch(m, d_text, foff, d_words, nw, runs, stats);
   if (debug())
     fprintf(stderr, "[inflate] at %.3f ms: lane %p: batch inflated and parsed in %.3f ms\n", ms_since(t_proc),
             (void*)m, ms_since(t0));
@@ -541,6 +542,7 @@ gg_status run_lane(gg_ctx* x, GzClaims& cl, uint64_t* d_sk, uint32_t* d_len, int
   std::vector<uint32_t> row_of;
   std::vector<uint64_t> out_rows;
   std::vector<uint32_t> out_lens;
+  std::vector<gg_genome_stats> batch_stats;
   for (;;) {
     GzStaged* g = pipe.next();
     if (!g) break;
@@ -555,11 +557,13 @@ gg_status run_lane(gg_ctx* x, GzClaims& cl, uint64_t* d_sk, uint32_t* d_len, int
       ~Hint() { m->scratch_hint = 1.0; }
     } hint{x};
     x->scratch_hint = g->at ? std::min(16.0, std::max(1.0, (double)gz_batch_bytes() / (double)g->at)) : 1.0;
-    const gg_status is = inflate_staged_batch(x, pipe, *g, cl, host_threads, &d_words, &nw, runs);
+    const gg_status is = inflate_staged_batch(x, pipe, *g, cl, host_threads, &d_words, &nw, runs,
+                                              cl.stats ? &batch_stats : nullptr);
     if (is != GG_OK) return is;
     const uint32_t ng = (uint32_t)g->idx.size();
     row_of.resize(ng);
     for (uint32_t q = 0; q < ng; ++q) row_of[q] = cl.row_of[g->idx[q]];
+    for (uint32_t q = 0; cl.stats && q < ng; ++q) cl.stats[row_of[q]] = batch_stats[q];  // (each row: one lane's)
     uint32_t* d_row_of;
     uint32_t* h_row_of;  // (pinned: a pageable copy blocks this thread; sketch_core syncs before the next batch)
     GG_HIP(x, scratch_t(x, "row_of", ng, &d_row_of));

@@ -317,6 +317,75 @@ bool device_parse() {
   return e && strcmp(e, "device") == 0;
 }
 
+// The assembly statistics of a parsed batch's files (parse.hip passes 4 and
+// 5; p: the batch's launch, its pre_nl on the device; bfile: the blocks'
+// files).  Per-file sums follow bfile on the host; the records' lengths come
+// back 8 bytes each and every file's n50 is finished here.  Synchronises st.
+gg_status stats_raw_batch(gg_ctx* m, ParseLaunch& p, uint32_t nf, const uint32_t* bfile, hipStream_t st,
+                          std::vector<gg_genome_stats>& out) {
+  const uint32_t nb = p.n_blocks;
+  out.assign(nf, gg_genome_stats{});
+  if (!nb) return GG_OK;
+  ParseStatsBlock *d_sb, *h_sb;
+  uint64_t *d_off, *h_off;  // rec_off [nb], then file_rec0 [nf + 1]
+  GG_HIP(m, scratch_t(m, "stats_blk", nb, &d_sb));
+  GG_HIP(m, scratch_t(m, "stats_off", (size_t)nb + nf + 1, &d_off));
+  GG_HIP(m, host_scratch_t(m, "stats_blk_host", nb, &h_sb));
+  GG_HIP(m, host_scratch_t(m, "stats_off_host", (size_t)nb + nf + 1, &h_off));
+  p.stats_blk = d_sb;
+  GG_HIP(m, timed_launch(m, GG_KERNEL_PARSE, 0, st, [&] { return parse_batch_pass(4, p, st); }));
+  GG_HIP(m, hipMemcpyAsync(h_sb, d_sb, nb * sizeof(ParseStatsBlock), hipMemcpyDeviceToHost, st));
+  GG_HIP(m, hipStreamSynchronize(st));
+  // per file: records and N / n along bfile; then every block's record
+  // offset.  A block that opens no record only adds its head bytes to the
+  // record open at its entry: summed here (carry) -- on the device they
+  // would be a chain of atomics on one address per contig -- so pass 5 runs
+  // over the blocks that open records (list) alone.
+  uint64_t* frec0 = h_off + nb;
+  for (uint32_t f = 0; f <= nf; ++f) frec0[f] = 0;
+  for (uint32_t b = 0; b < nb; ++b) {
+    frec0[bfile[b] + 1] += h_sb[b].recs;
+    out[bfile[b]].num_ambiguous_bases += h_sb[b].amb;
+  }
+  for (uint32_t f = 0; f < nf; ++f) frec0[f + 1] += frec0[f];
+  const uint64_t n_recs = frec0[nf];
+  uint32_t *d_list, *h_list;
+  GG_HIP(m, scratch_t(m, "stats_list", nb, &d_list));
+  GG_HIP(m, host_scratch_t(m, "stats_list_host", nb, &h_list));
+  std::vector<uint64_t> carry(n_recs, 0);
+  uint64_t acc = 0;
+  uint32_t n_list = 0;
+  for (uint32_t b = 0; b < nb; ++b) {
+    h_off[b] = acc;
+    if (h_sb[b].recs) h_list[n_list++] = b;
+    else if (acc > frec0[bfile[b]]) carry[acc - 1] += h_sb[b].head;  // (a record of this file is open)
+    acc += h_sb[b].recs;
+  }
+  uint64_t *d_len, *h_len;
+  GG_HIP(m, scratch_t(m, "stats_len", std::max<uint64_t>(n_recs, 1), &d_len));
+  GG_HIP(m, host_scratch_t(m, "stats_len_host", std::max<uint64_t>(n_recs, 1), &h_len));
+  if (n_list) {
+    GG_HIP(m, hipMemcpyAsync(d_off, h_off, ((size_t)nb + nf + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    GG_HIP(m, hipMemcpyAsync(d_list, h_list, n_list * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    GG_HIP(m, hipMemsetAsync(d_len, 0, n_recs * sizeof(uint64_t), st));
+    p.rec_off = d_off;
+    p.file_rec0 = d_off + nb;
+    p.n_recs = n_recs;
+    p.contig_len = d_len;
+    p.stats_list = d_list;
+    p.n_stats_blocks = n_list;
+    GG_HIP(m, timed_launch(m, GG_KERNEL_PARSE, 0, st, [&] { return parse_batch_pass(5, p, st); }));
+    GG_HIP(m, hipMemcpyAsync(h_len, d_len, n_recs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    GG_HIP(m, hipStreamSynchronize(st));
+  }
+  for (uint64_t r = 0; r < n_recs; ++r) h_len[r] += carry[r];
+  for (uint32_t f = 0; f < nf; ++f) {
+    const uint64_t amb = out[f].num_ambiguous_bases;
+    out[f] = finish_genome_stats(h_len + frec0[f], frec0[f + 1] - frec0[f], amb);
+  }
+  return GG_OK;
+}
+
 }  // namespace
 
 // One batch of FASTA text, already in device memory (d_text, files at
@@ -324,7 +393,7 @@ bool device_parse() {
 // m), runs of >= k bases (genome = file index in the batch, base = packed
 // position) into runs.  Synchronises m->stream.
 gg_status parse_raw_batch(gg_ctx* m, const uint8_t* d_text, const std::vector<uint64_t>& foff, uint32_t** d_words,
-                          uint64_t* n_words, std::vector<gg_run>& runs) {
+                          uint64_t* n_words, std::vector<gg_run>& runs, std::vector<gg_genome_stats>* stats) {
   hipStream_t st = m->stream;
   const uint32_t nf = (uint32_t)foff.size() - 1;
   const uint64_t bb = parse_block_bytes();
@@ -473,6 +542,11 @@ gg_status parse_raw_batch(gg_ctx* m, const uint8_t* d_text, const std::vector<ui
     if (e - a >= (uint64_t)m->k) runs.push_back(gg_run{f, (uint32_t)(e - a), a});
   }
   stamp("runs");
+  if (stats) {
+    const gg_status ss = stats_raw_batch(m, p, nf, bfile, st, *stats);
+    if (ss != GG_OK) return ss;
+    stamp("stats");
+  }
   return GG_OK;
 }
 
@@ -483,10 +557,14 @@ namespace {
 // cache_dir are read from it (every member receives those rows from the
 // host); the others are packed on the host threads and sketched in batches
 // (each batch: pinned staging -> H2D -> K1 with a row map), and stored in
-// the cache.  host_out / host_lens (optional) receive the rows.
+// the cache.  host_out / host_lens (optional) receive the rows.  out_stats
+// (optional, gg_sketch_files_stats): every genome's assembly statistics from
+// the same read -- the cache is then not read (they need the bytes), only
+// written.
 gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const char* const* paths, uint32_t n,
                                const char* cache_dir, std::vector<Rows>& rows, std::vector<RowSpan>& spans,
-                               uint64_t* host_out, uint32_t* host_lens, uint32_t* n_cached) {
+                               uint64_t* host_out, uint32_t* host_lens, uint32_t* n_cached,
+                               gg_genome_stats* out_stats = nullptr) {
   const size_t M = ms.size();
   const uint32_t s = c->s;
   rows.assign(M, Rows{});
@@ -498,7 +576,7 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
   std::vector<uint8_t> hit(n, 0);
   std::vector<uint64_t> hit_rows;  // [hits * s]
   std::vector<uint32_t> hit_lens;  // [n]
-  if (cache_dir) {
+  if (cache_dir && !out_stats) {
     hit_lens.assign(n, 0);
     constexpr uint32_t kChunk = 1024;
     std::vector<uint64_t> chunk((size_t)std::min(n, kChunk) * s);
@@ -541,12 +619,14 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
   // gzip lists: ingest_gz.cpp's stagers read the files; otherwise the
   // PackStream workers read (and pack) them
   std::unique_ptr<PackStream> streamp;
-  if (!gz_dev) streamp.reset(new PackStream(miss.data(), nm, c->k, c->host_threads, budget, cache_dir != nullptr, raw));
+  if (!gz_dev) streamp.reset(new PackStream(miss.data(), nm, c->k, c->host_threads, budget, cache_dir != nullptr, raw,
+                                             out_stats != nullptr));
   GzClaims claims;
   claims.paths = miss.data();
   claims.row_of = miss_at.data();
   claims.n = nm;
   claims.cache_dir = cache_dir;
+  claims.stats = out_stats;
   claims.stagers = (uint32_t)(M * gz_lane_count());
   std::mutex cursor_mu;
   uint32_t cursor = 0;
@@ -578,6 +658,7 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
     std::vector<uint32_t> row_of;
     std::vector<uint64_t> out_rows;
     std::vector<uint32_t> out_lens;
+    std::vector<gg_genome_stats> batch_stats;
     for (;;) {
       uint32_t b0, b1;
       {
@@ -630,8 +711,9 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
         GG_HIP(m, scratch_t(m, "stage_text", std::max<uint64_t>(foff.back(), 1), &d_text));
         if (foff.back())
           GG_HIP(m, hipMemcpyAsync(d_text, m->pinned, foff.back(), hipMemcpyHostToDevice, m->stream));
-        const gg_status ps = parse_raw_batch(m, d_text, foff, &d_words, &nw, runs);
+        const gg_status ps = parse_raw_batch(m, d_text, foff, &d_words, &nw, runs, out_stats ? &batch_stats : nullptr);
         if (ps != GG_OK) return ps;
+        for (size_t q = 0; out_stats && q < row_of.size(); ++q) out_stats[row_of[q]] = batch_stats[q];
       }
       for (uint32_t i = b0; !raw && i < b1; ++i, ++g) {
         const std::vector<uint32_t>* w;
@@ -654,6 +736,7 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
         if (!w->empty()) memcpy((uint32_t*)stage + nw, w->data(), w->size() * sizeof(uint32_t));
         for (const gg_run& x : *rr) runs.push_back(gg_run{g, x.len, x.base + nw * 16});
         row_of.push_back(miss_at[i]);
+        if (out_stats) out_stats[miss_at[i]] = stream.stats(i);
         nw += w->size();
         stream.release(i);
         if (nw >= kBatchWords && i + 1 < b1) {  // large genomes: cut the batch here, return the rest
@@ -983,6 +1066,19 @@ gg_status gg_sketch_files(gg_ctx* ctx, const char* const* paths, uint32_t n_path
   std::vector<Rows> rows;
   std::vector<RowSpan> spans;
   return sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, out_hashes, out_lens, n_cached);
+}
+
+gg_status gg_sketch_files_stats(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, const char* cache_dir,
+                                uint64_t* out_hashes, uint32_t* out_lens, gg_genome_stats* out_stats) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  if (n_paths && (!paths || !out_hashes || !out_lens || !out_stats))
+    return fail(ctx, GG_ERR_INVALID_ARG, "gg_sketch_files_stats: null argument");
+  if (n_paths == 0) return GG_OK;
+  const std::vector<gg_ctx*> ms = members(ctx);
+  std::vector<Rows> rows;
+  std::vector<RowSpan> spans;
+  return sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, out_hashes, out_lens, nullptr,
+                              out_stats);
 }
 
 gg_status gg_precluster_files_cached(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,

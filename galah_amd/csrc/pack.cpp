@@ -87,8 +87,23 @@ struct GenomePacker {
   uint32_t fill = 0;  // bases in cur
   uint64_t run_start = 0;
   bool in_run = false;
+  // Assembly statistics (src/genome_stats.rs:11-51), taken in the same walk
+  // when want_stats: a record's length is its sequence bytes other than
+  // '\n' and '\r' (blanks and every letter count), its ambiguous bases the
+  // N / n among them.
+  bool want_stats = false;
+  uint64_t rec_len = 0, n_ambiguous = 0;
+  std::vector<uint64_t> contig_lens;
+  gg_genome_stats stats{};  // (finish())
 
   explicit GenomePacker(int k_) : k(k_) {}
+
+  // a sequence byte that is no base
+  inline void count_other(uint8_t b) {
+    if (b == '\n' || b == '\r') return;
+    ++rec_len;
+    n_ambiguous += (b | 0x20) == 'n';
+  }
 
   inline void push(uint32_t c) {
     cur |= c << (30 - 2 * fill);
@@ -167,7 +182,9 @@ struct GenomePacker {
   // time: all bases (the common case) in one step; otherwise the bases
   // before the first other byte in one step, then that byte (a line break
   // of a 60-column file costs one step, not one per byte up to it).
-  void add_sequence(const uint8_t* p, size_t n) {
+  // (S: the record's statistics in the same steps.)
+  template <bool S>
+  void add_sequence_t(const uint8_t* p, size_t n) {
     size_t i = 0;
     while (i < n) {
       uint32_t word;
@@ -175,15 +192,18 @@ struct GenomePacker {
         const uint32_t m = pack16(p + i, &word);
         if (m == 0xFFFFu) {
           push16(word);
+          if (S) rec_len += 16;
           i += 16;
           continue;
         }
         const uint32_t j = (uint32_t)__builtin_ctz(~m);  // leading bases
         if (j) {
           push_n(word, j);
+          if (S) rec_len += j;
           i += j;
         }
         if (kClass.t[p[i]] == kBreak) end_run();  // (else whitespace: skipped)
+        if (S) count_other(p[i]);
         ++i;
         continue;
       }
@@ -194,13 +214,25 @@ struct GenomePacker {
           run_start = n_bases;
         }
         push(c);
-      } else if (c == kBreak) {
-        end_run();
+        if (S) ++rec_len;
+      } else {
+        if (c == kBreak) end_run();
+        if (S) count_other(p[i]);
       }
       ++i;
     }
   }
-  void end_record() { end_run(); }
+  void add_sequence(const uint8_t* p, size_t n) {
+    if (want_stats) add_sequence_t<true>(p, n);
+    else add_sequence_t<false>(p, n);
+  }
+  void end_record() {
+    end_run();
+    if (want_stats) {
+      contig_lens.push_back(rec_len);
+      rec_len = 0;
+    }
+  }
 
   void finish() {
     end_run();
@@ -209,6 +241,7 @@ struct GenomePacker {
       cur = 0;
       fill = 0;
     }
+    if (want_stats) stats = finish_genome_stats(contig_lens.data(), contig_lens.size(), n_ambiguous);
   }
 };
 
@@ -529,8 +562,10 @@ bool read_file(const char* path, std::vector<uint8_t>& buf, std::string& err) {
 // Parses FASTA ('>') or FASTQ ('@') as needletail 0.5 does for well-formed
 // files; anything else is a format error (galah: "Failed to sketch genomes
 // with finch", src/finch.rs:50).
-gg_status pack_buffer(const uint8_t* d, size_t n, const char* name,
-                      GenomePacker& gp, std::string& err) {
+// (Sink: what takes each record's sequence bytes -- the packer, or the
+// statistics alone.)
+template <class Sink>
+gg_status walk_records(const uint8_t* d, size_t n, const char* name, Sink& gp, std::string& err) {
   if (n == 0 || (d[0] != '>' && d[0] != '@')) {
     err = std::string("not a FASTA/FASTQ file: ") + name;
     return GG_ERR_FORMAT;
@@ -568,6 +603,30 @@ gg_status pack_buffer(const uint8_t* d, size_t n, const char* name,
   }
   return GG_OK;
 }
+gg_status pack_buffer(const uint8_t* d, size_t n, const char* name, GenomePacker& gp, std::string& err) {
+  return walk_records(d, n, name, gp, err);
+}
+
+// The statistics of src/genome_stats.rs:11-51 alone, from the same record
+// walk (gg_genome_stats_files): a record's length is its sequence bytes
+// other than '\n' and '\r', its ambiguous bases the N / n among them.
+struct StatsSink {
+  uint64_t rec_len = 0, n_ambiguous = 0;
+  std::vector<uint64_t> contig_lens;
+  void add_sequence(const uint8_t* p, size_t n) {
+    uint64_t breaks = 0, amb = 0;
+    for (size_t i = 0; i < n; ++i) {
+      breaks += (p[i] == '\n') | (p[i] == '\r');
+      amb += (p[i] | 0x20) == 'n';
+    }
+    rec_len += n - breaks;
+    n_ambiguous += amb;
+  }
+  void end_record() {
+    contig_lens.push_back(rec_len);
+    rec_len = 0;
+  }
+};
 
 // Raw streams: the text the device parser reads.  A file that starts with
 // '>' is FASTA to its end (pack_buffer splits records only at lines that
@@ -675,6 +734,23 @@ int default_threads() {
 
 int ingest_threads(int n_threads) { return n_threads > 0 ? n_threads : default_threads(); }
 
+gg_genome_stats finish_genome_stats(uint64_t* lens, uint64_t n, uint64_t n_ambiguous) {
+  gg_genome_stats r{n, n_ambiguous, 0, 0};
+  for (uint64_t i = 0; i < n; ++i) r.total_bases += lens[i];
+  // src/genome_stats.rs:34-44
+  std::sort(lens, lens + n);
+  const uint64_t cutoff = r.total_bases / 2;
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    sum += lens[i];
+    if (sum >= cutoff) {
+      r.n50 = lens[i];
+      break;
+    }
+  }
+  return r;
+}
+
 // ---------------------------------------------------------------------------
 // PackStream: files packed on a worker pool, handed to consumers genome by
 // genome with bounded host memory (see gg_internal.hpp).
@@ -686,6 +762,7 @@ struct PackStream::Impl {
   uint64_t budget;
   bool stamping = false;
   bool raw = false;
+  bool stats = false;
   std::vector<FileStamp> stamps;
   std::mutex mu;
   std::condition_variable cv_done;   // a genome finished packing
@@ -714,6 +791,7 @@ struct PackStream::Impl {
         state[i] = 1;
       }
       auto gp = std::make_unique<GenomePacker>(k);
+      gp->want_stats = stats && !raw;
       gg_status s = GG_OK;
       std::string e;
       if (stamping) file_stamp(paths[i], &stamps[i]);
@@ -743,11 +821,12 @@ struct PackStream::Impl {
 };
 
 PackStream::PackStream(const char* const* paths, uint32_t n, int k, int n_threads, uint64_t budget_bytes,
-                       bool stamp_files, bool raw)
+                       bool stamp_files, bool raw, bool stats)
     : p_(new Impl()) {
   Impl& m = *p_;
   m.stamping = stamp_files;
   m.raw = raw;
+  m.stats = stats;
   m.stamps.resize(stamp_files ? n : 0);
   m.paths = paths;
   m.n = n;
@@ -820,6 +899,11 @@ gg_status host_text_from_bytes(std::vector<uint8_t>& bytes, const char* name, st
 FileStamp PackStream::stamp(uint32_t i) {
   std::lock_guard<std::mutex> lk(p_->mu);
   return p_->stamping ? p_->stamps[i] : FileStamp{};
+}
+
+gg_genome_stats PackStream::stats(uint32_t i) {
+  std::lock_guard<std::mutex> lk(p_->mu);
+  return p_->state[i] == 2 && p_->g[i] ? p_->g[i]->stats : gg_genome_stats{};
 }
 
 void PackStream::release(uint32_t i) {
@@ -901,6 +985,50 @@ extern "C" gg_status gg_pack_files(const char* const* paths, uint32_t n_paths,
     return GG_ERR_OUT_OF_MEMORY;
   }
   *out = p;
+  return GG_OK;
+}
+
+extern "C" gg_status gg_genome_stats_files(const char* const* paths, uint32_t n_paths, int n_threads,
+                                           gg_genome_stats* out) {
+  if ((n_paths && (!paths || !out))) {
+    set_thread_error("gg_genome_stats_files: invalid argument");
+    return GG_ERR_INVALID_ARG;
+  }
+  std::vector<gg_status> st(n_paths, GG_OK);
+  std::vector<std::string> errs(n_paths);
+  if (n_threads <= 0) n_threads = default_threads();
+  n_threads = (int)std::min<uint32_t>((uint32_t)n_threads, std::max(1u, n_paths));
+  std::atomic<uint32_t> next{0};
+  auto worker = [&]() {
+    std::vector<uint8_t> buf;
+    for (;;) {
+      const uint32_t i = next.fetch_add(1);
+      if (i >= n_paths) break;
+      out[i] = gg_genome_stats{};
+      if (!paths[i]) {
+        st[i] = GG_ERR_INVALID_ARG;
+        errs[i] = "null path";
+        continue;
+      }
+      if (!read_file(paths[i], buf, errs[i])) {
+        st[i] = GG_ERR_IO;
+        continue;
+      }
+      StatsSink sink;
+      st[i] = walk_records(buf.data(), buf.size(), paths[i], sink, errs[i]);
+      if (st[i] == GG_OK) out[i] = finish_genome_stats(sink.contig_lens.data(), sink.contig_lens.size(), sink.n_ambiguous);
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < n_threads; ++t) th.emplace_back(worker);
+  worker();
+  for (auto& t : th) t.join();
+  for (uint32_t i = 0; i < n_paths; ++i) {
+    if (st[i] != GG_OK) {
+      set_thread_error(errs[i]);
+      return st[i];
+    }
+  }
   return GG_OK;
 }
 

@@ -27,6 +27,8 @@
 //      (assembled in LDS) and every run start.
 // Passes 2 and 3 classify a thread's 32 bytes bit-parallel (parse_core.hpp:
 // masks, carry chains, compress) with two rounds of block scans each.
+// Passes 4 and 5 (further down) are the assembly statistics of the same
+// text, for the callers that ask for them.
 #include "device_util.hpp"
 #include "gg_internal.hpp"
 #include "parse_core.hpp"
@@ -135,32 +137,45 @@ struct Chunk {
   parse::Roles r;
   uint32_t rel;  // block-relative index of byte 0
 };
-__device__ __forceinline__ Chunk chunk_roles(const BlockArgs& a, uint64_t b0, uint64_t b1, uint64_t fstart,
-                                             uint64_t pre_nl, uint32_t (*sh)[2]) {
-  Chunk c;
-  c.rel = threadIdx.x * kPerThread;
-  const uint64_t i0 = b0 + c.rel;
+// The thread's words (w), their masks and where byte 0 stands on its line.
+struct ChunkLines {
   uint32_t w[8];
+  parse::Masks m;
+  bool line0, hdr0;
+};
+__device__ __forceinline__ ChunkLines chunk_lines(const BlockArgs& a, uint64_t b0, uint64_t b1, uint64_t fstart,
+                                                  uint64_t pre_nl, uint32_t (*sh)[2]) {
+  ChunkLines c;
+  const uint32_t rel = threadIdx.x * kPerThread;
+  const uint64_t i0 = b0 + rel;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const uint64_t at = i0 + 16 * h;
     uint4 v = make_uint4(0x20202020u, 0x20202020u, 0x20202020u, 0x20202020u);
     if (at < b1) v = *(const uint4*)(a.raw + at);
-    w[4 * h] = v.x;
-    w[4 * h + 1] = v.y;
-    w[4 * h + 2] = v.z;
-    w[4 * h + 3] = v.w;
+    c.w[4 * h] = v.x;
+    c.w[4 * h + 1] = v.y;
+    c.w[4 * h + 2] = v.z;
+    c.w[4 * h + 3] = v.w;
   }
   const uint32_t lim = b1 > i0 ? (uint32_t)min<uint64_t>(b1 - i0, kPerThread) : 0u;
-  c.m = parse::classify(w, lim);
-  const uint32_t nlv = c.m.nl ? c.rel + 32u - (uint32_t)parse::clz(c.m.nl) : 0u;  // (last '\n': relative index + 1)
+  c.m = parse::classify(c.w, lim);
+  const uint32_t nlv = c.m.nl ? rel + 32u - (uint32_t)parse::clz(c.m.nl) : 0u;  // (last '\n': relative index + 1)
   uint32_t ex, exs, tm, ts;
   block_scan(nlv, 0, sh, ex, exs, tm, ts);
   const uint64_t nlp = ex ? b0 + ex : pre_nl;       // (absolute index + 1, 0: none)
   const uint64_t ls = nlp > fstart ? nlp : fstart;  // the line start of byte 0 (<= i0)
-  const bool line0 = ls == i0;
-  const bool hdr0 = !line0 && ls < a.n && a.raw[ls] == '>';
-  c.r = parse::roles(c.m, line0, hdr0);
+  c.line0 = ls == i0;
+  c.hdr0 = !c.line0 && ls < a.n && a.raw[ls] == '>';
+  return c;
+}
+__device__ __forceinline__ Chunk chunk_roles(const BlockArgs& a, uint64_t b0, uint64_t b1, uint64_t fstart,
+                                             uint64_t pre_nl, uint32_t (*sh)[2]) {
+  const ChunkLines l = chunk_lines(a, b0, b1, fstart, pre_nl, sh);
+  Chunk c;
+  c.rel = threadIdx.x * kPerThread;
+  c.m = l.m;
+  c.r = parse::roles(l.m, l.line0, l.hdr0);
   return c;
 }
 
@@ -284,6 +299,94 @@ __global__ __launch_bounds__(kThreads) void parse_emit_kernel(BlockArgs a, const
   }
 }
 
+// ---------------------------------------------------------------------------
+// Assembly statistics of the batch's genomes (src/genome_stats.rs:11-51),
+// from the text the parser reads: two more passes, launched only for the
+// calls that ask for them (gg_sketch_files_stats), after pass 1 (they need
+// its line-start prefix).
+//   4. per block: the records it opens, its N / n, and the sequence bytes in
+//      front of its first record start (they belong to the record open at
+//      block entry);
+//   5. with the exclusive scan of the record counts: every record's length
+//      summed into contig_len[], over the blocks that open a record (list;
+//      the host adds the pass-4 counts of the others itself: on the device
+//      they were one chain of same-address atomics per contig).  A block
+//      sums per record in LDS first, so a (block, record) pair costs one
+//      global atomic at most, and a record opened and closed inside one
+//      block a plain store.
+// Nothing crosses a file: the blocks do not straddle files, the '\n' padding
+// between files counts as nothing, and a file's first block has no record
+// open at entry.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMaxBlockRecs = kBlockBytes / 2;  // (a record start needs a line of its own: '>' '\n')
+
+__device__ __forceinline__ parse::StatRoles chunk_stats(const BlockArgs& a, uint64_t b0, uint64_t b1, uint64_t fstart,
+                                                        uint64_t pre_nl, uint32_t (*sh)[2]) {
+  const ChunkLines l = chunk_lines(a, b0, b1, fstart, pre_nl, sh);
+  return parse::stat_roles(l.w, l.m, l.line0, l.hdr0);
+}
+
+__global__ __launch_bounds__(kThreads) void parse_stats_count_kernel(BlockArgs a, const uint64_t* __restrict__ blk_end,
+                                                                    const uint64_t* __restrict__ pre_nl,
+                                                                    ParseStatsBlock* __restrict__ out) {
+  __shared__ uint32_t sh1[kThreads / 64][2], sh2[kThreads / 64][2], sh3[kThreads / 64][2];
+  const uint32_t b = blockIdx.x;
+  const uint64_t b0 = a.blk_start[b], b1 = blk_end[b];
+  const parse::StatRoles r = chunk_stats(a, b0, b1, a.file_start[a.blk_file[b]], pre_nl[b], sh1);
+  // records and N / n: block sums (<= 4096 and <= 8192: 16 bits each); a
+  // record start in a chunk before this one: exclusive max
+  uint32_t before, exs, any, tot;
+  block_scan(r.rec ? 1u : 0u, (uint32_t)parse::popc(r.rec) | ((uint32_t)parse::popc(r.amb) << 16), sh2, before, exs, any,
+             tot);
+  const uint32_t head = before ? 0u : (uint32_t)parse::popc(parse::below_first(r.seq, r.rec));
+  uint32_t exm, exh, tm, tot_head;
+  block_scan(0, head, sh3, exm, exh, tm, tot_head);
+  if (threadIdx.x == 0) out[b] = ParseStatsBlock{tot & 0xFFFFu, tot >> 16, tot_head, 0u};
+}
+
+__global__ __launch_bounds__(kThreads) void parse_stats_emit_kernel(BlockArgs a, const uint64_t* __restrict__ blk_end,
+                                                                   const uint64_t* __restrict__ pre_nl,
+                                                                   const ParseStatsBlock* __restrict__ blk,
+                                                                   const uint32_t* __restrict__ list,
+                                                                   const uint64_t* __restrict__ rec_off,
+                                                                   const uint64_t* __restrict__ file_rec0,
+                                                                   uint64_t n_recs,
+                                                                   unsigned long long* __restrict__ contig_len) {
+  __shared__ uint32_t sh1[kThreads / 64][2], sh2[kThreads / 64][2];
+  __shared__ uint32_t lens[kMaxBlockRecs + 1];  // [0]: the record open at entry, [1 + r]: the block's record r
+  const uint32_t b = list[blockIdx.x];
+  const ParseStatsBlock sb = blk[b];
+  const uint32_t f = a.blk_file[b];
+  const uint64_t r0 = rec_off[b];        // records opened before the block (in the batch)
+  const bool open = r0 > file_rec0[f];   // ... one of them in this file: it is open at entry
+  if (sb.recs == 0) return;              // (not listed; uniform over the block)
+  const uint32_t nr = min(sb.recs, kMaxBlockRecs);
+  for (uint32_t i = threadIdx.x; i <= nr; i += kThreads) lens[i] = 0;
+  const uint64_t b0 = a.blk_start[b], b1 = blk_end[b];
+  const parse::StatRoles r = chunk_stats(a, b0, b1, a.file_start[f], pre_nl[b], sh1);
+  uint32_t exm, slot, tm, tot;
+  block_scan(0, (uint32_t)parse::popc(r.rec), sh2, exm, slot, tm, tot);  // slot: records opened before the chunk
+  // (lens is clear: the scans synchronised)
+  if (__all(r.rec == 0)) {  // one record over the whole wave: one LDS atomic
+    uint32_t v = (uint32_t)parse::popc(r.seq);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&lens[min(slot, nr)], v);
+  } else {
+    parse::record_counts(r, [&](uint32_t t, uint32_t c) { atomicAdd(&lens[min(slot + t, nr)], c); });
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i <= nr; i += kThreads) {
+    const uint32_t v = lens[i];
+    const uint64_t at = r0 + i - 1;  // (i == 0 without an open record: unused)
+    if (i == 0 ? !open : at >= n_recs) continue;
+    if (i == 0 || i == nr) {  // other blocks add to these two
+      if (v) atomicAdd(&contig_len[at], (unsigned long long)v);
+    } else {
+      contig_len[at] = v;
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t parse_batch_pass(int pass, const ParseLaunch& p, hipStream_t st) {
@@ -300,6 +403,14 @@ hipError_t parse_batch_pass(int pass, const ParseLaunch& p, hipStream_t st) {
     case 3:
       hipLaunchKernelGGL(parse_emit_kernel, grid, block, 0, st, a, p.blk_end, p.pre_nl, p.pre_last, p.base_off,
                          p.run_off, p.words, p.starts);
+      break;
+    case 4:
+      hipLaunchKernelGGL(parse_stats_count_kernel, grid, block, 0, st, a, p.blk_end, p.pre_nl, p.stats_blk);
+      break;
+    case 5:
+      hipLaunchKernelGGL(parse_stats_emit_kernel, dim3(p.n_stats_blocks), block, 0, st, a, p.blk_end, p.pre_nl,
+                         p.stats_blk, p.stats_list, p.rec_off,
+                         p.file_rec0, p.n_recs, (unsigned long long*)p.contig_len);
       break;
     default:
       return hipErrorInvalidValue;

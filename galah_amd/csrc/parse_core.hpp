@@ -160,6 +160,57 @@ GG_PC_FN Roles roles(const Masks& m, bool line0, bool hdr0) {
   return r;
 }
 
+// Assembly statistics (parse.hip's stats passes; src/genome_stats.rs:11-51):
+// a record opens at every header line's '>', its length is the bytes of its
+// sequence lines other than '\n' and '\r' (every other byte counts: blanks,
+// IUPAC letters, a '>' inside a line), its ambiguous bases are their N / n.
+// bit j of the result = byte j of the word equals the byte repeated in pat
+GG_PC_FN uint32_t eq_bytes(uint32_t w, uint32_t pat) {
+  const uint32_t z = zero_bytes(w ^ pat) >> 7;  // bits 0, 8, 16, 24
+  return (z | (z >> 7) | (z >> 14) | (z >> 21)) & 0xFu;
+}
+struct StatRoles {
+  uint32_t rec;  // a record opens here (the '>' at the start of a line)
+  uint32_t seq;  // counts in the open record's length
+  uint32_t amb;  // ... and is N or n
+};
+// w, lim as for classify (m = classify(w, lim)); line0, hdr0 as for roles
+GG_PC_FN StatRoles stat_roles(const uint32_t (&w)[8], const Masks& m, bool line0, bool hdr0) {
+  uint32_t cr = 0, nn = 0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    cr |= eq_bytes(w[q], 0x0D0D0D0Du) << (4 * q);
+    nn |= eq_bytes(w[q] | 0x20202020u, 0x6E6E6E6Eu) << (4 * q);
+  }
+  const uint32_t ls = (m.nl << 1) | (line0 ? 1u : 0u);  // line starts
+  StatRoles r;
+  r.rec = ls & m.gt;
+  const uint32_t hdr = fill(r.rec, ~ls, hdr0);  // bytes on header lines
+  r.seq = ~(hdr | m.nl | m.past | cr);
+  r.amb = r.seq & nn;
+  return r;
+}
+
+// the bits of x below m's lowest set bit (all of x when m == 0)
+GG_PC_FN uint32_t below_first(uint32_t x, uint32_t m) { return m ? x & ((m & (0u - m)) - 1u) : x; }
+// The 32 bytes' sequence bytes per record: f(t, n) with n > 0 bytes for the
+// record open at byte 0 (t = 0) and for the t-th record the bytes open (t =
+// 1 .. popc(r.rec)), in order.
+template <class F>
+GG_PC_FN void record_counts(const StatRoles& r, F&& f) {
+  uint32_t t = 0;
+  const uint32_t c0 = (uint32_t)popc(below_first(r.seq, r.rec));
+  if (c0) f(t, c0);
+  for (uint32_t m = r.rec; m;) {
+    const uint32_t j = (uint32_t)ctz(m);
+    m &= m - 1u;
+    ++t;
+    const uint32_t after = ~(((1u << j) << 1) - 1u);  // the bytes after the '>'
+    const uint32_t c = (uint32_t)popc(below_first(r.seq & after, m));
+    if (c) f(t, c);
+  }
+}
+
 // run starts: a base whose last kept byte before it is not a base (prev_base:
 // the last kept byte before the 32 is a base)
 GG_PC_FN uint32_t run_starts(const Roles& r, bool prev_base) {

@@ -7,6 +7,7 @@
 //   src/finch.rs:26-75 finch::distances(...)              galah::finch_distances(...)
 //   src/sorted_pair_genome_distance_cache.rs:4-59         galah::SortedPairGenomeDistanceCache
 //   src/cluster_argument_parsing.rs:1160-1182             galah::parse_percentage
+//   src/genome_stats.rs:4-51                              galah::GenomeAssemblyStats, calculate_genome_stats
 //
 // Errors: the reference panics ("Failed to sketch genomes with finch",
 // src/finch.rs:50); here the same message is thrown as std::runtime_error.
@@ -207,5 +208,27 @@ class FinchPreclusterer : public PreclusterDistanceFinder {
   size_t num_kmers;
   uint8_t kmer_length;
 };
+
+// src/genome_stats.rs:4-9 (#[derive(Debug, PartialEq)])
+struct GenomeAssemblyStats {
+  size_t num_contigs;
+  size_t num_ambiguous_bases;
+  size_t n50;
+  bool operator==(const GenomeAssemblyStats& o) const {
+    return num_contigs == o.num_contigs && num_ambiguous_bases == o.num_ambiguous_bases && n50 == o.n50;
+  }
+  bool operator!=(const GenomeAssemblyStats& o) const { return !(*this == o); }
+};
+
+// src/genome_stats.rs:11-51 on the host (gg_genome_stats_files); the
+// reference's panic message for a file that does not read or parse
+inline GenomeAssemblyStats calculate_genome_stats(const std::string& fasta_path) {
+  const char* p = fasta_path.c_str();
+  gg_genome_stats s{};
+  if (gg_genome_stats_files(&p, 1, 1, &s) != GG_OK)
+    throw std::runtime_error("Failed to calculate genome statistics for file '" + fasta_path + "': " +
+                             gg_thread_last_error());
+  return GenomeAssemblyStats{(size_t)s.num_contigs, (size_t)s.num_ambiguous_bases, (size_t)s.n50};
+}
 
 }  // namespace galah

@@ -119,7 +119,7 @@ int gg_device(const gg_ctx* ctx);
  * n_devices == 0, the GALAHGPU_DEVICES environment variable (comma-separated
  * ordinals) when it is set and every visible device otherwise -- galah's
  * `n_gpus = 0` ("all").  One resolved device gives a plain single-device
- * context.  gg_sketch, gg_pairs, gg_sketch_files, gg_precluster_files(_cached)
+ * context.  gg_sketch, gg_pairs, gg_sketch_files(_stats), gg_precluster_files(_cached)
  * and gg_precluster_shards use every member; the other entry points act on
  * the first member.  Results never depend on the device list. */
 gg_ctx* gg_create_multi(int kmer_length, uint32_t sketch_size, uint64_t hash_seed,
@@ -278,6 +278,41 @@ gg_status gg_precluster_files_cached(gg_ctx* ctx, const char* const* paths, uint
                                      float min_ani, const char* cache_dir, gg_pair** pairs,
                                      float** ani, uint64_t* n_out, uint32_t* n_cached);
 
+/* ---- genome assembly statistics (src/genome_stats.rs) ------------------- */
+/* What galah orders the genomes by before it clusters them (the default
+ * quality formulas, src/cluster_argument_parsing.rs:721-811):
+ * calculate_genome_stats of src/genome_stats.rs:11-51.  A record is what the
+ * packer treats as one; num_contigs counts them (empty ones too); a contig's
+ * length is the bytes of its sequence lines other than '\n' and '\r';
+ * num_ambiguous_bases the N and n among them; n50 the reference's loop
+ * (lengths ascending, the first at which the running sum reaches
+ * total_bases / 2 -- not the textbook N50); total_bases the sum of the
+ * lengths (the reference does not return it). */
+typedef struct gg_genome_stats {
+  uint64_t num_contigs;
+  uint64_t num_ambiguous_bases;
+  uint64_t n50;
+  uint64_t total_bases;
+} gg_genome_stats;
+
+/* src/genome_stats.rs:11 for each file, on n_threads host threads (<= 0: as
+ * gg_pack_files); no device, no ctx.  File errors as gg_pack_files reports
+ * them (GG_ERR_IO, GG_ERR_FORMAT; the lowest failing index). */
+gg_status gg_genome_stats_files(const char* const* paths, uint32_t n_paths,
+                                int n_threads, gg_genome_stats* out);
+
+/* gg_sketch_files plus the statistics of every genome, from one read of
+ * each file: the host packer takes them in its record walk, the device
+ * ingest paths (device gzip inflate, GALAHGPU_PARSE=device) in a pass over
+ * the batch text resident on the device.  The sketch cache is never read
+ * (the statistics need the bytes); with a cache_dir every sketch computed is
+ * stored, so a following gg_precluster_files_cached over the same files, in
+ * any order, finds them all.  Uses every member of a multi-device context;
+ * results do not depend on the device list. */
+gg_status gg_sketch_files_stats(gg_ctx* ctx, const char* const* paths, uint32_t n_paths,
+                                const char* cache_dir, uint64_t* out_hashes,
+                                uint32_t* out_lens, gg_genome_stats* out_stats);
+
 /* ---- after distances(): preclusters -------- */
 /* src/clusterer.rs:409-431 partition_sketches (single linkage over the
  * pairs the cache contains) + :45-57 (each set sorted ascending, sets
@@ -335,7 +370,8 @@ void gg_free(void* p);
  * member: the block-start search (work: compressed bytes of the batch), the
  * sub-span decode (tokens written), the expand and the resolve (text bytes),
  * the CRC-32 (text bytes), the three parse passes (text bytes, counted on
- * the first) and the PCIe upload of each staged batch (bytes). */
+ * the first; gg_sketch_files_stats adds its two statistics passes to them)
+ * and the PCIe upload of each staged batch (bytes). */
 enum { GG_KERNEL_SKETCH = 0, GG_KERNEL_FINALIZE = 1, GG_KERNEL_PAIRS = 2, GG_KERNEL_PAIRS_INDEX = 3,
        GG_KERNEL_INFLATE_SEARCH = 4, GG_KERNEL_INFLATE_DECODE = 5, GG_KERNEL_INFLATE_EXPAND = 6,
        GG_KERNEL_INFLATE_RESOLVE = 7, GG_KERNEL_INFLATE_CRC = 8, GG_KERNEL_PARSE = 9, GG_KERNEL_UPLOAD = 10,

@@ -133,6 +133,17 @@ pub struct gg_kernel_stats {
     pub work: u64,
 }
 
+/// A genome's assembly statistics (`gg_genome_stats`; galah's
+/// `GenomeAssemblyStats`, src/genome_stats.rs:4-9, plus the total length).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gg_genome_stats {
+    pub num_contigs: u64,
+    pub num_ambiguous_bases: u64,
+    pub n50: u64,
+    pub total_bases: u64,
+}
+
 /// `gg_pair_sink`: a block of compared pairs; return 0 to go on.
 pub type gg_pair_sink = Option<unsafe extern "C" fn(user: *mut c_void, pairs: *const gg_pair, n: u64) -> c_int>;
 
@@ -199,6 +210,13 @@ extern "C" {
     pub fn gg_precluster_files_cached(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
                                       cache_dir: *const c_char, pairs: *mut *mut gg_pair, ani: *mut *mut f32,
                                       n_out: *mut u64, n_cached: *mut u32) -> GgStatus;
+
+    // genome assembly statistics (src/genome_stats.rs)
+    pub fn gg_genome_stats_files(paths: *const *const c_char, n_paths: u32, n_threads: c_int,
+                                 out: *mut gg_genome_stats) -> GgStatus;
+    pub fn gg_sketch_files_stats(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32,
+                                 cache_dir: *const c_char, out_hashes: *mut u64, out_lens: *mut u32,
+                                 out_stats: *mut gg_genome_stats) -> GgStatus;
 
     // after distances(): preclusters
     pub fn gg_partition_preclusters(n_genomes: u32, pairs: *const gg_pair, n_pairs: u64, members: *mut u32,
