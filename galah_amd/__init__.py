@@ -31,6 +31,7 @@ __all__ = [
     "partition_preclusters", "precluster_pairs", "preclusters", "LOCAL_PAIR_DTYPE",
     "sketch_cache_load", "sketch_cache_store",
     "GenomeAssemblyStats", "calculate_genome_stats", "genome_stats", "STATS_DTYPE",
+    "cluster_pairs_host", "clusters_from_reps", "ClusterDistanceFinder", "FinchClusterer", "cluster",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "gg_create_multi", "gg_device_count", "gg_device_ctx", "gg_set_host_threads", "gg_phase_times",
     "gg_precluster_shards", "gg_fallbacks", "gg_peer_links", "gg_info_line", "gg_precluster_files_each",
     "gg_genome_stats_files", "gg_sketch_files_stats",
+    "gg_cluster_pairs_host", "gg_cluster_pairs", "gg_cluster_pairs_device", "gg_clusters_from_reps", "gg_cluster_files",
 )
 
 GG_OK = 0
@@ -162,6 +164,12 @@ _sig("gg_synth_mixed_device", _i32, [_vp, _u32, _u32, _vp, _u32, ctypes.c_float,
                                      _u64, ctypes.POINTER(_u64), _vp])
 _sig("gg_partition_preclusters", _i32, [_u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32)])
 _sig("gg_precluster_pairs", _i32, [_u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp])
+_sig("gg_cluster_pairs_host", _i32, [_u32, _vp, _vp, _u64, ctypes.c_float, _vp])
+_sig("gg_cluster_pairs", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float, _vp])
+_sig("gg_cluster_pairs_device", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float, _vp, _vp])
+_sig("gg_clusters_from_reps", _i32, [_u32, _vp, _vp, _vp, ctypes.POINTER(_u32)])
+_sig("gg_cluster_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_float,
+                                ctypes.c_char_p, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
 
 
 class _KStats(ctypes.Structure):
@@ -179,6 +187,7 @@ KERNEL_SKETCH, KERNEL_FINALIZE, KERNEL_PAIRS, KERNEL_PAIRS_INDEX = 0, 1, 2, 3
 # the device-inflate ingest's kernels (gzip lists through precluster_files / sketch_files)
 (KERNEL_INFLATE_SEARCH, KERNEL_INFLATE_DECODE, KERNEL_INFLATE_EXPAND, KERNEL_INFLATE_RESOLVE, KERNEL_INFLATE_CRC,
  KERNEL_PARSE, KERNEL_UPLOAD) = range(4, 11)
+KERNEL_CLUSTER = 11  # every kernel of cluster_pairs / cluster_pairs_device (work: pairs)
 INGEST_KERNELS = {"search": KERNEL_INFLATE_SEARCH, "decode": KERNEL_INFLATE_DECODE, "expand": KERNEL_INFLATE_EXPAND,
                   "resolve": KERNEL_INFLATE_RESOLVE, "crc": KERNEL_INFLATE_CRC, "parse": KERNEL_PARSE,
                   "upload": KERNEL_UPLOAD}
@@ -290,6 +299,48 @@ def preclusters(n_genomes, pairs):
     a list of ascending index lists, largest first."""
     members, offsets = partition_preclusters(n_genomes, pairs)
     return [members[offsets[s]:offsets[s + 1]].tolist() for s in range(len(offsets) - 1)]
+
+
+def _pairs_ani_arg(pairs, ani):
+    """(PAIR_DTYPE array, f32 array) of a pair list and its ANI values: a
+    structured array with i and j, or a sequence of (i, j) tuples."""
+    if not (isinstance(pairs, np.ndarray) and pairs.dtype.names):
+        ij = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        pairs = np.zeros(len(ij), dtype=PAIR_DTYPE)
+        pairs["i"], pairs["j"] = ij[:, 0], ij[:, 1]
+    p = pairs if pairs.dtype == PAIR_DTYPE and pairs.flags.c_contiguous else _as_pairs(pairs)
+    a = np.ascontiguousarray(ani, dtype=np.float32)
+    if a.shape != (len(p),):
+        raise ValueError("one ani per pair")
+    return p, a
+
+
+def cluster_pairs_host(n_genomes, pairs, ani, cluster_ani):
+    """src/clusterer.rs:155-225 and :316-406 with the clusterer reusing the
+    preclusterer's values (finch + finch), from the pair cache alone ->
+    rep_of [n_genomes] u32 (rep_of[r] == r for a representative).  pairs in
+    either orientation, any order; ani the f32 the cache stores for each.
+    Host C++ (gg_cluster_pairs_host), linear in the pairs."""
+    p, a = _pairs_ani_arg(pairs, ani)
+    rep_of = np.zeros(max(n_genomes, 1), np.uint32)
+    st = _L.gg_cluster_pairs_host(n_genomes, _ptr(p), _ptr(a), len(p), ctypes.c_float(cluster_ani), _ptr(rep_of))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return rep_of[:n_genomes]
+
+
+def clusters_from_reps(rep_of):
+    """rep_of -> the clusters as lists of indices: by representative
+    ascending, the representative first, then its members ascending."""
+    rep_of = np.ascontiguousarray(rep_of, dtype=np.uint32)
+    n = len(rep_of)
+    members = np.zeros(max(n, 1), np.uint32)
+    offsets = np.zeros(n + 1, np.uint32)
+    nc = _u32()
+    st = _L.gg_clusters_from_reps(n, _ptr(rep_of), _ptr(members), _ptr(offsets), ctypes.byref(nc))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return [members[offsets[c]:offsets[c + 1]].tolist() for c in range(nc.value)]
 
 
 def sketch_cache_load(cache_dir, path, k=21, s=1000, seed=0):
@@ -698,6 +749,35 @@ class Context:
             raise self._err(st)
         return self._pairs_ani(pp, ap, cnt.value)
 
+    def cluster_pairs(self, n_genomes, pairs, ani, cluster_ani):
+        """cluster_pairs_host on the context's (first) device -> rep_of."""
+        p, a = _pairs_ani_arg(pairs, ani)
+        rep_of = np.zeros(max(n_genomes, 1), np.uint32)
+        st = _L.gg_cluster_pairs(self._c, n_genomes, _ptr(p), _ptr(a), len(p), ctypes.c_float(cluster_ani),
+                                 _ptr(rep_of))
+        if st != GG_OK:
+            raise self._err(st)
+        return rep_of[:n_genomes]
+
+    def cluster_files(self, paths, min_ani, cluster_ani, cache_dir=None, want_pairs=True):
+        """precluster_files(min_ani) followed by cluster_pairs(cluster_ani)
+        in one call -> (rep_of, pairs, ani), or rep_of alone with
+        want_pairs=False (the library then frees the pairs)."""
+        n = len(paths)
+        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        rep_of = np.zeros(max(n, 1), np.uint32)
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        st = _L.gg_cluster_files(self._c, arr, n, ctypes.c_float(min_ani), ctypes.c_float(cluster_ani),
+                                 None if cache_dir is None else os.fsencode(cache_dir), _ptr(rep_of),
+                                 ctypes.byref(pp) if want_pairs else None, ctypes.byref(ap) if want_pairs else None,
+                                 ctypes.byref(cnt) if want_pairs else None)
+        if st != GG_OK:
+            raise self._err(st)
+        if not want_pairs:
+            return rep_of[:n]
+        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
+        return rep_of[:n], pairs, ani
+
     def precluster_files_each(self, paths, min_ani, each, cache_dir=None):
         """precluster_files, and every compared pair (i < j, all N (N - 1) / 2,
         whatever the ANI) handed to each(block) in (i, j) order as PAIR_DTYPE
@@ -743,6 +823,16 @@ class Context:
         st = _L.gg_pairs_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, tile_begin, tile_end,
                                 ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
                                 None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+
+    def cluster_pairs_device(self, n_genomes, d_pairs, d_ani, n_pairs, cluster_ani, d_rep_of, stream=None):
+        """cluster_pairs over device-resident tensors: d_pairs n_pairs 16-byte
+        gg_pair records, d_ani f32, d_rep_of u32 [n_genomes] (every entry is
+        written).  Synchronises the stream; the input is not checked."""
+        st = _L.gg_cluster_pairs_device(self._c, n_genomes, _dev_ptr(d_pairs), _dev_ptr(d_ani), n_pairs,
+                                        ctypes.c_float(cluster_ani), _dev_ptr(d_rep_of),
+                                        None if stream is None else stream)
         if st != GG_OK:
             raise self._err(st)
 
@@ -951,3 +1041,80 @@ class FinchPreclusterer(PreclusterDistanceFinder):
 
     def method_name(self):
         return "finch"
+
+
+class ClusterDistanceFinder:
+    """src/lib.rs:29-37."""
+
+    def initialise(self):
+        raise NotImplementedError
+
+    def method_name(self):
+        raise NotImplementedError
+
+    def get_ani_threshold(self):
+        raise NotImplementedError
+
+    def calculate_ani(self, fasta1, fasta2):
+        raise NotImplementedError
+
+
+class FinchClusterer(ClusterDistanceFinder):
+    """A finch clusterer: the ClusterDistanceFinder whose value for a pair is
+    the one FinchPreclusterer stores (the original design of
+    src/clusterer.rs, find_minhash_representatives / find_minhash_memberships;
+    galah's CLUSTER_METHODS has no finch).  ani is a fraction (f32)."""
+
+    def __init__(self, ani, num_kmers=1000, kmer_length=21):
+        self.ani = np.float32(ani)
+        self.num_kmers = int(num_kmers)
+        self.kmer_length = int(kmer_length)
+
+    def initialise(self):
+        pass
+
+    def method_name(self):
+        return "finch"
+
+    def get_ani_threshold(self):
+        return self.ani
+
+    def calculate_ani(self, fasta1, fasta2):
+        """Option<f32>: the two files through precluster_files at min_ani 0."""
+        _, ani = _context(self.kmer_length, self.num_kmers).precluster_files([fasta1, fasta2], 0.0)
+        return np.float32(ani[0]) if len(ani) else None
+
+
+def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
+    """src/clusterer.rs:14-125 -> the clusters as lists of genome indices,
+    each with its representative first.  Built for the case the reference
+    marks skip_clusterer (:29-33): preclusterer and clusterer both "finch",
+    the result then being a function of the pair cache, computed on the GPU
+    (gg_cluster_files).  Any other combination raises: the external-clusterer
+    flow is not part of this library."""
+    log = logging.getLogger("galah")
+    clusterer.initialise()
+    pre_name, clu_name = preclusterer.method_name(), clusterer.method_name()
+    log.info("Preclustering with %s and clustering with %s", pre_name, clu_name)  # :24-27
+    if not (pre_name == clu_name == "finch"):
+        raise NotImplementedError("galah_amd.cluster: only finch + finch (the clusterer reusing the preclusterer's "
+                                  "ANI values) runs here, not %s + %s" % (pre_name, clu_name))
+    log.info("Preclustering and clustering methods are the same, so reusing ANI values")  # :31
+    paths = list(genomes)
+    cache_dir = sketch_cache_dir if sketch_cache_dir is not None else getattr(preclusterer, "sketch_cache_dir", None)
+    try:
+        ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
+        log.info("Sketching MinHash representations of each genome with finch ..")  # src/finch.rs:46
+        rep_of, pairs, _ = ctx.cluster_files(paths, float(np.float32(preclusterer.min_ani)),
+                                             float(np.float32(clusterer.get_ani_threshold())), cache_dir=cache_dir)
+    except GalahGpuError as e:
+        raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+    log.info("Finished sketching genomes")  # src/finch.rs:48
+    log.info(ctx.info_line())
+    log.info("Preclustering ..")  # :38
+    if paths:
+        _, offsets = partition_preclusters(len(paths), pairs)
+        log.info("Found %d preclusters. The largest contained %d genomes", len(offsets) - 1,
+                 int(offsets[1] - offsets[0]))  # :59-63
+    log.info("Finding representative genomes and assigning all genomes to these ..")  # :65
+    return clusters_from_reps(rep_of)

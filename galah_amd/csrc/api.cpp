@@ -1550,6 +1550,13 @@ gg_status gg_info_line(const gg_ctx* ctx, char* buf, size_t cap) {
     snprintf(line, sizeof line, "; index->gate by cost %llu", (unsigned long long)costly);
     out += line;
   }
+  // the last gg_cluster_pairs(_device) call (on the first member): launches
+  // of its representative-round kernel
+  const gg_ctx* first = ctx->devs.empty() ? ctx : ctx->devs[0];
+  if (first->cluster_calls) {
+    snprintf(line, sizeof line, "; cluster round launches %llu", (unsigned long long)first->cluster_rounds);
+    out += line;
+  }
   // device / pinned scratch buffers grown since the context was created
   // (and the wall time that took: hipFree waits for the device), its lanes'
   // included -- a call that grows one runs long

@@ -153,6 +153,9 @@ struct gg_ctx {
   // the largest inflate scratch of a batch on this lane (tokens, sub-span
   // areas, val, text), bytes: the per-lane footprint the info line reports
   uint64_t gz_scratch_bytes = 0;
+  // gg_cluster_pairs(_device) calls on this device, and the launches of the
+  // representative-round kernel in the last one (gg_info_line)
+  uint64_t cluster_calls = 0, cluster_rounds = 0;
   // scratch / host-scratch buffers regrown (and the wall ms it took), gg_info_line
   uint64_t scratch_regrows = 0;
   double scratch_regrow_ms = 0;
@@ -235,6 +238,14 @@ constexpr uint64_t kDeviceSortPairs = 4096;  // pairs_range_to_host sorts this m
 gg_status pairs_range_to_host(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                               uint64_t tb, uint64_t te, float min_ani, std::vector<gg_pair>& res,
                               hipStream_t st);
+
+// The finch + finch clustering step over device-resident pairs (cluster.hip):
+// rep_of[] by the rules of cluster_core.hpp.  Synchronises st.
+gg_status cluster_device(gg_ctx* c, uint32_t n, const gg_pair* d_pairs, const float* d_ani, uint64_t n_pairs, float T,
+                         uint32_t* d_rep_of, hipStream_t st);
+// The input checks of its host-input forms (cluster.cpp; the thread's error is set).
+gg_status cluster_check_input(const char* who, uint32_t n_genomes, const gg_pair* pairs, const float* ani,
+                              uint64_t n_pairs, float cluster_ani, const uint32_t* rep_of);
 
 // A batch of files inflated on m's device (inflate_host.cpp): h_in (pinned,
 // in_bytes) holds files[f]'s bytes; *d_text receives the batch's FASTA text,

@@ -5,6 +5,8 @@
 //   src/lib.rs:23-27   trait PreclusterDistanceFinder     galah::PreclusterDistanceFinder
 //   src/finch.rs:4-24  struct FinchPreclusterer           galah::FinchPreclusterer
 //   src/finch.rs:26-75 finch::distances(...)              galah::finch_distances(...)
+//   src/lib.rs:29-37   trait ClusterDistanceFinder        galah::ClusterDistanceFinder, FinchClusterer
+//   src/clusterer.rs:14-125 cluster(...)                  galah::cluster (finch + finch)
 //   src/sorted_pair_genome_distance_cache.rs:4-59         galah::SortedPairGenomeDistanceCache
 //   src/cluster_argument_parsing.rs:1160-1182             galah::parse_percentage
 //   src/genome_stats.rs:4-51                              galah::GenomeAssemblyStats, calculate_genome_stats
@@ -208,6 +210,95 @@ class FinchPreclusterer : public PreclusterDistanceFinder {
   size_t num_kmers;
   uint8_t kmer_length;
 };
+
+// src/lib.rs:29-37
+class ClusterDistanceFinder {
+ public:
+  virtual ~ClusterDistanceFinder() = default;
+  virtual void initialise() = 0;
+  virtual const char* method_name() const = 0;
+  virtual float get_ani_threshold() const = 0;
+  virtual std::optional<float> calculate_ani(const std::string& fasta1, const std::string& fasta2) = 0;
+};
+
+// A finch clusterer: its value for a pair is the one FinchPreclusterer
+// stores (the original design of src/clusterer.rs, find_minhash_representatives
+// / find_minhash_memberships; galah's CLUSTER_METHODS has no finch).
+class FinchClusterer : public ClusterDistanceFinder {
+ public:
+  FinchClusterer(float ani, size_t num_kmers = 1000, uint8_t kmer_length = 21)
+      : ani(ani), num_kmers(num_kmers), kmer_length(kmer_length) {}
+  void initialise() override {}
+  const char* method_name() const override { return "finch"; }
+  float get_ani_threshold() const override { return ani; }
+  // the two files through finch_distances at min_ani 0 (info lines muted)
+  std::optional<float> calculate_ani(const std::string& fasta1, const std::string& fasta2) override {
+    auto saved = info_sink();
+    info_sink() = nullptr;
+    SortedPairGenomeDistanceCache d;
+    try {
+      d = finch_distances({fasta1, fasta2}, 0.0f, num_kmers, kmer_length);
+    } catch (...) {
+      info_sink() = saved;
+      throw;
+    }
+    info_sink() = saved;
+    const auto* v = d.get({0, 1});
+    return v ? *v : std::nullopt;
+  }
+
+  float ani;  // fraction, not percentage
+  size_t num_kmers;
+  uint8_t kmer_length;
+};
+
+// src/clusterer.rs:14-125 -> the clusters as lists of genome indices, each
+// with its representative first, by representative ascending (the reference
+// assembles its list in rayon completion order, :114-121).  Built for the
+// case the reference marks skip_clusterer (:29-33): a FinchPreclusterer with
+// a clusterer whose method_name() is also "finch", the result then being a
+// function of the pair cache, computed on the GPU (gg_cluster_files).  Any
+// other combination throws std::invalid_argument: the external-clusterer flow
+// is not part of this library.
+inline std::vector<std::vector<size_t>> cluster(const std::vector<std::string>& genomes,
+                                                PreclusterDistanceFinder& preclusterer,
+                                                ClusterDistanceFinder& clusterer) {
+  clusterer.initialise();
+  const std::string pre_name = preclusterer.method_name(), clu_name = clusterer.method_name();
+  info("Preclustering with " + pre_name + " and clustering with " + clu_name);  // :24-27
+  const auto* finch = dynamic_cast<const FinchPreclusterer*>(&preclusterer);
+  if (!finch || pre_name != "finch" || clu_name != "finch")
+    throw std::invalid_argument("galah::cluster: only finch + finch (the clusterer reusing the preclusterer's ANI "
+                                "values) runs here, not " + pre_name + " + " + clu_name);
+  info("Preclustering and clustering methods are the same, so reusing ANI values");  // :31
+  gg_status st = GG_OK;
+  gg_ctx* ctx = gg_create_multi(finch->kmer_length, (uint32_t)finch->num_kmers, 0, nullptr, 0, &st);
+  if (!ctx) throw std::runtime_error(std::string("Failed to sketch genomes with finch: ") + gg_thread_last_error());
+  gg_set_host_threads(ctx, current_num_threads());
+  std::vector<const char*> c_paths;
+  for (const auto& p : genomes) c_paths.push_back(p.c_str());
+  const uint32_t n = (uint32_t)genomes.size();
+  std::vector<uint32_t> rep_of(n), members(n), offsets((size_t)n + 1);
+  info("Sketching MinHash representations of each genome with finch ..");  // src/finch.rs:46
+  st = gg_cluster_files(ctx, c_paths.data(), n, finch->min_ani, clusterer.get_ani_threshold(), nullptr, rep_of.data(),
+                        nullptr, nullptr, nullptr);
+  if (st != GG_OK) {
+    const std::string msg = gg_last_error(ctx);
+    gg_destroy(ctx);
+    throw std::runtime_error("Failed to sketch genomes with finch: " + msg);  // src/finch.rs:50
+  }
+  info("Finished sketching genomes");  // src/finch.rs:48
+  char line[1024];
+  if (gg_info_line(ctx, line, sizeof line) == GG_OK) info(line);
+  gg_destroy(ctx);
+  info("Finding representative genomes and assigning all genomes to these ..");  // :65
+  uint32_t nc = 0;
+  if (gg_clusters_from_reps(n, rep_of.data(), members.data(), offsets.data(), &nc) != GG_OK)
+    throw std::runtime_error(gg_thread_last_error());
+  std::vector<std::vector<size_t>> out(nc);
+  for (uint32_t c = 0; c < nc; ++c) out[c].assign(members.begin() + offsets[c], members.begin() + offsets[c + 1]);
+  return out;
+}
 
 // src/genome_stats.rs:4-9 (#[derive(Debug, PartialEq)])
 struct GenomeAssemblyStats {

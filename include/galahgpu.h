@@ -346,6 +346,54 @@ gg_status gg_precluster_pairs(uint32_t n_genomes, const gg_pair* pairs,
                               const uint32_t* offsets, uint32_t n_sets,
                               gg_local_pair* out, uint64_t* pair_offsets);
 
+/* ---- finch + finch clustering ---------------------------- */
+/* src/clusterer.rs:14-125 when the preclusterer and the clusterer are both
+ * finch (skip_clusterer, :29-33, :180-185): the result is a function of the
+ * pair cache alone.  n_genomes genomes in the caller's order (galah's
+ * quality order: an earlier genome is preferred as representative); pairs in
+ * either orientation and any order, each unordered pair at most once, only
+ * their i and j are read; ani[p] the f32 the cache stores for pair p
+ * (gg_ani_f32, the ani[] of gg_precluster_files); cluster_ani an f32
+ * fraction, below, equal to or above the precluster threshold.
+ *   :155-225  genome i is a representative unless a representative j < i has
+ *             a cached pair with it and ani >= cluster_ani (f32, :212);
+ *   :316-406  every other genome joins the representative, lower or higher,
+ *             with the largest cached ani; ties go to the smallest index.
+ * rep_of[g] receives genome g's representative (rep_of[r] == r for a
+ * representative).  The host-input forms return GG_ERR_INVALID_ARG for an
+ * index >= n_genomes, i == j, a NaN ani, a NaN cluster_ani or
+ * n_pairs >= 2^31. */
+
+/* On the host; no device, no ctx.  Linear in the pairs. */
+gg_status gg_cluster_pairs_host(uint32_t n_genomes, const gg_pair* pairs, const float* ani,
+                                uint64_t n_pairs, float cluster_ani, uint32_t* rep_of);
+/* The same on the context's (first) device: host arrays in, rep_of out. */
+gg_status gg_cluster_pairs(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* pairs, const float* ani,
+                           uint64_t n_pairs, float cluster_ani, uint32_t* rep_of);
+/* Device-resident d_pairs, d_ani and d_rep_of, on the given stream.
+ * Synchronises the stream internally (the representative rounds are
+ * launched until a word read back says no genome is undecided).  The input
+ * is not checked: a pair with an index >= n_genomes or i == j is ignored,
+ * NaN never compares >=, duplicates of a pair count once each. */
+gg_status gg_cluster_pairs_device(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* d_pairs,
+                                  const float* d_ani, uint64_t n_pairs, float cluster_ani,
+                                  uint32_t* d_rep_of, void* stream);
+/* rep_of -> CSR: cluster c is members[offsets[c] .. offsets[c+1]), clusters
+ * by representative ascending, the representative first, then its members
+ * ascending (galah assembles its list in rayon completion order,
+ * src/clusterer.rs:114-121: no output of galah depends on an order).
+ * members has n_genomes entries, offsets n_genomes + 1 (caller-owned).
+ * Host only.  GG_ERR_INVALID_ARG unless rep_of[rep_of[g]] == rep_of[g] < n. */
+gg_status gg_clusters_from_reps(uint32_t n_genomes, const uint32_t* rep_of, uint32_t* members,
+                                uint32_t* offsets, uint32_t* n_clusters);
+/* gg_precluster_files_cached(min_ani, cache_dir) followed by
+ * gg_cluster_pairs(cluster_ani) over its pairs; rep_of has n_paths entries.
+ * pairs / ani / n_out may all be NULL (the pairs are then freed), else they
+ * receive what gg_precluster_files_cached returns. */
+gg_status gg_cluster_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                           float cluster_ani, const char* cache_dir, uint32_t* rep_of,
+                           gg_pair** pairs, float** ani, uint64_t* n_out);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);
@@ -371,11 +419,13 @@ void gg_free(void* p);
  * sub-span decode (tokens written), the expand and the resolve (text bytes),
  * the CRC-32 (text bytes), the three parse passes (text bytes, counted on
  * the first; gg_sketch_files_stats adds its two statistics passes to them)
- * and the PCIe upload of each staged batch (bytes). */
+ * and the PCIe upload of each staged batch (bytes).  GG_KERNEL_CLUSTER is
+ * every kernel of gg_cluster_pairs(_device) (work: pairs, counted on the
+ * first). */
 enum { GG_KERNEL_SKETCH = 0, GG_KERNEL_FINALIZE = 1, GG_KERNEL_PAIRS = 2, GG_KERNEL_PAIRS_INDEX = 3,
        GG_KERNEL_INFLATE_SEARCH = 4, GG_KERNEL_INFLATE_DECODE = 5, GG_KERNEL_INFLATE_EXPAND = 6,
        GG_KERNEL_INFLATE_RESOLVE = 7, GG_KERNEL_INFLATE_CRC = 8, GG_KERNEL_PARSE = 9, GG_KERNEL_UPLOAD = 10,
-       GG_KERNEL_COUNT = 11 };
+       GG_KERNEL_CLUSTER = 11, GG_KERNEL_COUNT = 12 };
 typedef struct gg_kernel_stats {
   double ms;
   uint64_t launches;

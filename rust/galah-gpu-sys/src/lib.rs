@@ -49,7 +49,8 @@ pub const GG_KERNEL_INFLATE_RESOLVE: c_int = 7;
 pub const GG_KERNEL_INFLATE_CRC: c_int = 8;
 pub const GG_KERNEL_PARSE: c_int = 9;
 pub const GG_KERNEL_UPLOAD: c_int = 10;
-pub const GG_KERNEL_COUNT: c_int = 11;
+pub const GG_KERNEL_CLUSTER: c_int = 11;
+pub const GG_KERNEL_COUNT: c_int = 12;
 
 pub const GG_PATH_INDEX: c_int = 0;
 pub const GG_PATH_INDEX_ABANDONED: c_int = 1;
@@ -224,6 +225,20 @@ extern "C" {
     pub fn gg_precluster_pairs(n_genomes: u32, pairs: *const gg_pair, n_pairs: u64, members: *const u32,
                                offsets: *const u32, n_sets: u32, out: *mut gg_local_pair, pair_offsets: *mut u64)
         -> GgStatus;
+
+    // finch + finch clustering (src/clusterer.rs:155-225, :316-406 with skip_clusterer)
+    pub fn gg_cluster_pairs_host(n_genomes: u32, pairs: *const gg_pair, ani: *const f32, n_pairs: u64,
+                                 cluster_ani: f32, rep_of: *mut u32) -> GgStatus;
+    pub fn gg_cluster_pairs(ctx: *mut gg_ctx, n_genomes: u32, pairs: *const gg_pair, ani: *const f32, n_pairs: u64,
+                            cluster_ani: f32, rep_of: *mut u32) -> GgStatus;
+    pub fn gg_cluster_pairs_device(ctx: *mut gg_ctx, n_genomes: u32, d_pairs: *const gg_pair, d_ani: *const f32,
+                                   n_pairs: u64, cluster_ani: f32, d_rep_of: *mut u32, stream: *mut c_void)
+        -> GgStatus;
+    pub fn gg_clusters_from_reps(n_genomes: u32, rep_of: *const u32, members: *mut u32, offsets: *mut u32,
+                                 n_clusters: *mut u32) -> GgStatus;
+    pub fn gg_cluster_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
+                            cluster_ani: f32, cache_dir: *const c_char, rep_of: *mut u32, pairs: *mut *mut gg_pair,
+                            ani: *mut *mut f32, n_out: *mut u64) -> GgStatus;
 
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;
