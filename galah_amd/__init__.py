@@ -10,6 +10,9 @@ of libgalahgpu.so (include/galahgpu.h):
   src/sorted_pair_genome_distance_cache.rs:4-59        SortedPairGenomeDistanceCache
   src/cluster_argument_parsing.rs:1160-1182            parse_percentage()
   src/genome_stats.rs:4-51                             GenomeAssemblyStats, calculate_genome_stats()
+  src/cluster_validation.rs:7-78                       validate_clusters()
+  src/cluster_validation.rs:80-113                     read_clustering_file()
+  src/cluster_argument_parsing.rs:437-449, :478-484    write_cluster_definition(), write_representative_list()
 
 There is no CPU fallback: importing works without a GPU (so the ABI can be
 inspected), but every compute call needs a gfx950 device and raises
@@ -32,6 +35,8 @@ __all__ = [
     "sketch_cache_load", "sketch_cache_store",
     "GenomeAssemblyStats", "calculate_genome_stats", "genome_stats", "STATS_DTYPE",
     "cluster_pairs_host", "clusters_from_reps", "ClusterDistanceFinder", "FinchClusterer", "cluster",
+    "ani_pairs_host", "validate_clusters_host", "Validation", "ClusterValidation", "validate_clusters",
+    "read_clustering_file", "write_cluster_definition", "write_representative_list",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "gg_precluster_shards", "gg_fallbacks", "gg_peer_links", "gg_info_line", "gg_precluster_files_each",
     "gg_genome_stats_files", "gg_sketch_files_stats",
     "gg_cluster_pairs_host", "gg_cluster_pairs", "gg_cluster_pairs_device", "gg_clusters_from_reps", "gg_cluster_files",
+    "gg_ani_pairs_host", "gg_ani_pairs", "gg_ani_pairs_device",
+    "gg_validate_clusters_host", "gg_validate_clusters", "gg_validate_files",
 )
 
 GG_OK = 0
@@ -170,6 +177,21 @@ _sig("gg_cluster_pairs_device", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float
 _sig("gg_clusters_from_reps", _i32, [_u32, _vp, _vp, _vp, ctypes.POINTER(_u32)])
 _sig("gg_cluster_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_float,
                                 ctypes.c_char_p, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_ani_pairs_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _u64, _vp])
+_sig("gg_ani_pairs", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
+_sig("gg_ani_pairs_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
+
+
+class _Validation(ctypes.Structure):
+    _fields_ = [("member_pairs", ctypes.c_uint64), ("member_bad", ctypes.c_uint64), ("rep_pairs", ctypes.c_uint64),
+                ("rep_bad", ctypes.c_uint64)]
+
+
+_VOUT = [ctypes.POINTER(_Validation), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)]
+_sig("gg_validate_clusters_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _vp, _u32, ctypes.c_float] + _VOUT)
+_sig("gg_validate_clusters", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, ctypes.c_float] + _VOUT)
+_sig("gg_validate_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, _vp, _vp, _u32, ctypes.c_float,
+                                 ctypes.c_char_p] + _VOUT)
 
 
 class _KStats(ctypes.Structure):
@@ -188,6 +210,7 @@ KERNEL_SKETCH, KERNEL_FINALIZE, KERNEL_PAIRS, KERNEL_PAIRS_INDEX = 0, 1, 2, 3
 (KERNEL_INFLATE_SEARCH, KERNEL_INFLATE_DECODE, KERNEL_INFLATE_EXPAND, KERNEL_INFLATE_RESOLVE, KERNEL_INFLATE_CRC,
  KERNEL_PARSE, KERNEL_UPLOAD) = range(4, 11)
 KERNEL_CLUSTER = 11  # every kernel of cluster_pairs / cluster_pairs_device (work: pairs)
+KERNEL_ANI_PAIRS = 12  # the named-pair kernel of ani_pairs / ani_pairs_device / validate_clusters (work: listed pairs)
 INGEST_KERNELS = {"search": KERNEL_INFLATE_SEARCH, "decode": KERNEL_INFLATE_DECODE, "expand": KERNEL_INFLATE_EXPAND,
                   "resolve": KERNEL_INFLATE_RESOLVE, "crc": KERNEL_INFLATE_CRC, "parse": KERNEL_PARSE,
                   "upload": KERNEL_UPLOAD}
@@ -341,6 +364,170 @@ def clusters_from_reps(rep_of):
     if st != GG_OK:
         raise _thread_err(st)
     return [members[offsets[c]:offsets[c + 1]].tolist() for c in range(nc.value)]
+
+
+def _pair_list_arg(pairs):
+    """A fresh PAIR_DTYPE array naming the pairs (common and total zero): from
+    a structured array with i and j, or a sequence of (i, j)."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype.names:
+        p = np.zeros(len(pairs), dtype=PAIR_DTYPE)
+        p["i"], p["j"] = pairs["i"], pairs["j"]
+        return p
+    ij = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    p = np.zeros(len(ij), dtype=PAIR_DTYPE)
+    p["i"], p["j"] = ij[:, 0], ij[:, 1]
+    return p
+
+
+def _rows_arg(sketches, lens, sketch_size=None):
+    """(sketches [n, s] u64, lens [n] u32, n, s) of a sketch matrix."""
+    ln = np.ascontiguousarray(lens, dtype=np.uint32)
+    n = ln.shape[0]
+    sk = np.ascontiguousarray(sketches, dtype=np.uint64)
+    if n == 0:
+        return sk, ln, 0, int(sketch_size or 1)
+    if sk.ndim != 2 or sk.shape[0] != n or (sketch_size is not None and sk.shape[1] != sketch_size):
+        raise ValueError("sketches must be [n, sketch_size]")
+    return sk, ln, n, sk.shape[1]
+
+
+def _clusters_arg(clusters):
+    """(members u32, offsets u32, count) -- the CSR form of a list of index
+    lists, each with its representative first."""
+    sizes = [len(c) for c in clusters]
+    offsets = np.zeros(len(sizes) + 1, np.uint32)
+    np.cumsum(sizes, out=offsets[1:])
+    members = np.zeros(max(int(offsets[-1]), 1), np.uint32)
+    if offsets[-1]:
+        members[:offsets[-1]] = np.concatenate([np.asarray(c, dtype=np.uint32).reshape(-1) for c in clusters])
+    return members, offsets, len(sizes)
+
+
+class Validation:
+    """What validate_clusters found (src/cluster_validation.rs:7-78 with
+    finch's ANI): the four counts of gg_validation, and the violations as
+    PAIR_DTYPE records with their f32 ANI -- the members below the threshold
+    as (representative, member), then the representatives at or above it as
+    (r1 < r2)."""
+
+    def __init__(self, summary, bad, bad_ani):
+        self.member_pairs, self.member_bad = int(summary.member_pairs), int(summary.member_bad)
+        self.rep_pairs, self.rep_bad = int(summary.rep_pairs), int(summary.rep_bad)
+        self.bad, self.bad_ani = bad, bad_ani
+
+    @property
+    def ok(self):
+        return self.member_bad == 0 and self.rep_bad == 0
+
+    @property
+    def member_violations(self):
+        return self.bad[:self.member_bad], self.bad_ani[:self.member_bad]
+
+    @property
+    def rep_violations(self):
+        return self.bad[self.member_bad:], self.bad_ani[self.member_bad:]
+
+    def __repr__(self):
+        return ("Validation(member_pairs=%d, member_bad=%d, rep_pairs=%d, rep_bad=%d)"
+                % (self.member_pairs, self.member_bad, self.rep_pairs, self.rep_bad))
+
+
+def _take_validation(summary, bp, ap, cnt):
+    n = cnt.value
+    if n:
+        ani = np.empty(n, np.float32)
+        ctypes.memmove(ani.ctypes.data, ap.value, n * 4)
+    else:
+        ani = np.zeros(0, np.float32)
+    _L.gg_free(ap)
+    return Validation(summary, _take_pairs(bp, n), ani)
+
+
+def ani_pairs_host(sketches, lens, pairs, k=21):
+    """finch's merge counts and the stored f32 ANI of the pairs named
+    (src/lib.rs:29-37 calculate_ani for a whole list; gg_ani_pairs_host, no
+    device) -> (PAIR_DTYPE array in the order given, ani f32).  Either
+    orientation, repeats and i == j are allowed; there is no threshold."""
+    sk, ln, n, s = _rows_arg(sketches, lens)
+    p = _pair_list_arg(pairs)
+    ani = np.zeros(max(len(p), 1), np.float32)
+    st = _L.gg_ani_pairs_host(_ptr(sk), _ptr(ln), n, s, k, _ptr(p), len(p), _ptr(ani))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return p, ani[:len(p)]
+
+
+def validate_clusters_host(sketches, lens, clusters, ani, k=21):
+    """src/cluster_validation.rs:7-78 over sketches (gg_validate_clusters_host,
+    no device): clusters a list of index lists, each with its representative
+    first; ani the threshold as an f32 fraction -> Validation."""
+    sk, ln, n, s = _rows_arg(sketches, lens)
+    members, offsets, nc = _clusters_arg(clusters)
+    summary, bp, ap, cnt = _Validation(), _vp(), _vp(), _u64()
+    st = _L.gg_validate_clusters_host(_ptr(sk), _ptr(ln), n, s, k, _ptr(members), _ptr(offsets), nc,
+                                      ctypes.c_float(ani), ctypes.byref(summary), ctypes.byref(bp), ctypes.byref(ap),
+                                      ctypes.byref(cnt))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return _take_validation(summary, bp, ap, cnt)
+
+
+def read_clustering_file(path):
+    """src/cluster_validation.rs:80-113: a cluster definition file (as
+    write_cluster_definition, galah or dRep write it) -> the clusters as lists
+    of path strings, each with its representative first.  Tab-separated,
+    exactly two fields per line (ValueError otherwise); a line whose two
+    fields are equal opens a cluster; lines before the first such line are
+    dropped; a member line's first field is not compared with the open
+    representative; empty lines are skipped.  Unlike the reference's csv
+    reader, CSV quoting is not interpreted: a '"' is an ordinary byte."""
+    clusters, current, have_rep = [], [], False
+    with open(path, "r", encoding="utf-8", errors="surrogateescape", newline="") as f:
+        text = f.read()
+    for line in text.replace("\r\n", "\n").replace("\r", "\n").split("\n"):
+        if line == "":
+            continue
+        fields = line.split("\t")
+        if len(fields) != 2:
+            raise ValueError("Unexpectedly didn't find exactly 2 fields in clustering file: StringRecord([%s])"
+                             % ", ".join(_rust_str_debug(x) for x in fields))
+        if fields[0] == fields[1]:
+            if have_rep:
+                clusters.append(current)
+            current, have_rep = [], True
+        current.append(fields[1])
+    if have_rep:
+        clusters.append(current)
+    return clusters
+
+
+def _rust_str_debug(x):
+    return '"%s"' % x.replace("\\", "\\\\").replace('"', '\\"')
+
+
+def _write_lines(f, lines):
+    import io
+    if isinstance(f, (str, bytes, os.PathLike)):
+        with open(f, "wb") as g:
+            _write_lines(g, lines)
+        return
+    binary = isinstance(f, (io.RawIOBase, io.BufferedIOBase))
+    for line in lines:
+        f.write(os.fsencode(line) if binary else line)
+
+
+def write_cluster_definition(f, clusters, genomes):
+    """src/cluster_argument_parsing.rs:437-449 (--output-cluster-definition):
+    for every cluster, for every genome of it (the representative first, as
+    itself), "<representative>\\t<genome>\\n".  clusters: lists of indices into
+    genomes; f: a file object (text or binary) or a path."""
+    _write_lines(f, ("%s\t%s\n" % (genomes[c[0]], genomes[g]) for c in clusters for g in c))
+
+
+def write_representative_list(f, clusters, genomes):
+    """src/cluster_argument_parsing.rs:478-484 (--output-representative-list):
+    every cluster's representative, one per line."""
+    _write_lines(f, ("%s\n" % genomes[c[0]] for c in clusters))
 
 
 def sketch_cache_load(cache_dir, path, k=21, s=1000, seed=0):
@@ -759,6 +946,45 @@ class Context:
             raise self._err(st)
         return rep_of[:n_genomes]
 
+    def ani_pairs(self, sketches, lens, pairs):
+        """ani_pairs_host on the context's (first) device, one kernel launch
+        for the whole list -> (PAIR_DTYPE array in the order given, ani f32)."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        p = _pair_list_arg(pairs)
+        ani = np.zeros(max(len(p), 1), np.float32)
+        st = _L.gg_ani_pairs(self._c, _ptr(sk), _ptr(ln), n, _ptr(p), len(p), _ptr(ani))
+        if st != GG_OK:
+            raise self._err(st)
+        return p, ani[:len(p)]
+
+    def validate_clusters(self, sketches, lens, clusters, ani):
+        """validate_clusters_host on the device (gg_validate_clusters): the
+        members through the named-pair kernel, the representatives through
+        the all-pairs path -> Validation."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        members, offsets, nc = _clusters_arg(clusters)
+        summary, bp, ap, cnt = _Validation(), _vp(), _vp(), _u64()
+        st = _L.gg_validate_clusters(self._c, _ptr(sk), _ptr(ln), n, _ptr(members), _ptr(offsets), nc,
+                                     ctypes.c_float(ani), ctypes.byref(summary), ctypes.byref(bp), ctypes.byref(ap),
+                                     ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        return _take_validation(summary, bp, ap, cnt)
+
+    def validate_files(self, paths, clusters, ani, cache_dir=None):
+        """sketch_files(paths, cache_dir) followed by validate_clusters in one
+        call (gg_validate_files): clusters index paths -> Validation."""
+        n = len(paths)
+        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        members, offsets, nc = _clusters_arg(clusters)
+        summary, bp, ap, cnt = _Validation(), _vp(), _vp(), _u64()
+        st = _L.gg_validate_files(self._c, arr, n, _ptr(members), _ptr(offsets), nc, ctypes.c_float(ani),
+                                  None if cache_dir is None else os.fsencode(cache_dir), ctypes.byref(summary),
+                                  ctypes.byref(bp), ctypes.byref(ap), ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        return _take_validation(summary, bp, ap, cnt)
+
     def cluster_files(self, paths, min_ani, cluster_ani, cache_dir=None, want_pairs=True):
         """precluster_files(min_ani) followed by cluster_pairs(cluster_ani)
         in one call -> (rep_of, pairs, ani), or rep_of alone with
@@ -833,6 +1059,17 @@ class Context:
         st = _L.gg_cluster_pairs_device(self._c, n_genomes, _dev_ptr(d_pairs), _dev_ptr(d_ani), n_pairs,
                                         ctypes.c_float(cluster_ani), _dev_ptr(d_rep_of),
                                         None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+
+    def ani_pairs_device(self, d_sketches, d_lens, n, d_list, m, stream=None):
+        """ani_pairs over device-resident tensors: d_sketches [n, s] u64,
+        d_lens [n] u32, d_list m 16-byte gg_pair records whose common and total
+        are written in place (the integers only; ani_f32 gives the value).
+        Asynchronous; the input is not checked: an entry with an index >= n
+        receives 0 and 0."""
+        st = _L.gg_ani_pairs_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _dev_ptr(d_list), m,
+                                    None if stream is None else stream)
         if st != GG_OK:
             raise self._err(st)
 
@@ -1085,6 +1322,25 @@ class FinchClusterer(ClusterDistanceFinder):
         return np.float32(ani[0]) if len(ani) else None
 
 
+    def calculate_ani_many(self, pairs_of_paths, sketch_cache_dir=None):
+        """calculate_ani for a list of (fasta1, fasta2): every distinct file
+        sketched once (from sketch_cache_dir when it has it), then one
+        named-pair call -> a list of f32, in the order given."""
+        index, paths, named = {}, [], []
+        for a, b in pairs_of_paths:
+            for p in (a, b):
+                if p not in index:
+                    index[p] = len(paths)
+                    paths.append(p)
+            named.append((index[a], index[b]))
+        if not named:
+            return []
+        ctx = _context(self.kmer_length, self.num_kmers)
+        sk, lens, _ = ctx.sketch_files(paths, cache_dir=sketch_cache_dir)
+        _, ani = ctx.ani_pairs(sk, lens, named)
+        return [np.float32(a) for a in ani]
+
+
 def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
     """src/clusterer.rs:14-125 -> the clusters as lists of genome indices,
     each with its representative first.  Built for the case the reference
@@ -1118,3 +1374,97 @@ def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
                  int(offsets[1] - offsets[0]))  # :59-63
     log.info("Finding representative genomes and assigning all genomes to these ..")  # :65
     return clusters_from_reps(rep_of)
+
+
+def rust_f32(x):
+    """Rust's `{}` of an f32: the shortest round-trip digits, no exponent, no
+    trailing ".0"."""
+    return np.format_float_positional(np.float32(x), unique=True, trim="-")
+
+
+class ClusterValidation(Validation):
+    """validate_clusters' result: Validation's counts and records (indices
+    into .genomes, the distinct paths of the file in order of appearance),
+    the violations with their paths, and .ok.  .n_cached: genomes whose sketch
+    came from the sketch cache."""
+
+    def __init__(self, v, clusters, genomes, n_cached):
+        self.__dict__.update(v.__dict__)
+        self.clusters, self.genomes, self.n_cached = clusters, genomes, n_cached
+
+    def _with_paths(self, pairs, ani):
+        return [(self.genomes[int(p["i"])], self.genomes[int(p["j"])], np.float32(a)) for p, a in zip(pairs, ani)]
+
+    @property
+    def member_violation_paths(self):
+        """[(representative path, member path, f32 ANI)]"""
+        return self._with_paths(*self.member_violations)
+
+    @property
+    def rep_violation_paths(self):
+        """[(representative path, representative path, f32 ANI)]"""
+        return self._with_paths(*self.rep_violations)
+
+
+def validate_clusters(clustering_file, ani_threshold, num_kmers=1000, kmer_length=21, sketch_cache_dir=None):
+    """src/cluster_validation.rs:7-78 (galah cluster-validate) with finch's ANI
+    in FastANI's place: reads the cluster definition file, sketches every
+    distinct path once, checks every member against its representative
+    (>= ani_threshold) and every pair of representatives (< ani_threshold) on
+    the GPU -> ClusterValidation.  ani_threshold is a fraction (f32).  Logs
+    the reference's lines on the "galah" logger with "finch ANI" for
+    "FastANI" and the values as it prints them (percent: ani * 100 in f32):
+    "not ok" at error level, "ok" at debug level (the pairs in file order; a
+    representative against itself is not compared).  At debug level every
+    pair's value is fetched for those lines."""
+    log = logging.getLogger("galah")
+    thr = np.float32(ani_threshold)
+    named = read_clustering_file(clustering_file)
+    log.info("Read in %d clusters", len(named))  # :17
+    if log.isEnabledFor(logging.DEBUG):
+        log.debug("Clusters were: %s", _rust_pretty(named))  # :18
+    index, genomes = {}, []
+    for c in named:
+        for p in c:
+            if p not in index:
+                index[p] = len(genomes)
+                genomes.append(p)
+    clusters = [[index[p] for p in c] for c in named]
+    try:
+        ctx = _context(int(kmer_length), int(num_kmers))
+        sk, lens, n_cached = ctx.sketch_files(genomes, cache_dir=sketch_cache_dir)
+        v = ctx.validate_clusters(sk, lens, clusters, float(thr))
+    except GalahGpuError as e:
+        raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+    out = ClusterValidation(v, clusters, genomes, n_cached)
+    hundred = np.float32(100)
+    if log.isEnabledFor(logging.DEBUG):
+        member_list = [(c[0], g) for c in clusters for g in c[1:] if g != c[0]]
+        rep_list = [(clusters[a][0], clusters[b][0]) for a in range(len(clusters)) for b in range(a + 1, len(clusters))]
+        _, ani = ctx.ani_pairs(sk, lens, member_list + rep_list) if member_list or rep_list else (None, [])
+        for (r, g), a in zip(member_list, ani):
+            if np.float32(a) >= thr:
+                log.debug("finch ANI between %s and %s is ok: %s", genomes[r], genomes[g],
+                          rust_f32(np.float32(a) * hundred))
+        for (r1, r2), a in zip(rep_list, ani[len(member_list):]):
+            if np.float32(a) < thr:
+                log.debug("finch ANI between reps %s and %s is ok: %s", genomes[r1], genomes[r2],
+                          rust_f32(np.float32(a) * hundred))
+    for r, g, a in out.member_violation_paths:  # :31-34
+        log.error("finch ANI between %s and %s is not ok: %s", r, g, rust_f32(a * hundred))
+    for r1, r2, a in out.rep_violation_paths:  # :62-65
+        log.error("finch ANI between reps %s and %s is not ok: %s", r1, r2, rust_f32(a * hundred))
+    return out
+
+
+def _rust_pretty(clusters):
+    """Rust's `{:#?}` of a Vec<Vec<String>>."""
+    if not clusters:
+        return "[]"
+    out = ["["]
+    for c in clusters:
+        out.append("    [")
+        out.extend("        %s," % _rust_str_debug(p) for p in c)
+        out.append("    ],")
+    out.append("]")
+    return "\n".join(out)

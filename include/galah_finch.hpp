@@ -10,6 +10,9 @@
 //   src/sorted_pair_genome_distance_cache.rs:4-59         galah::SortedPairGenomeDistanceCache
 //   src/cluster_argument_parsing.rs:1160-1182             galah::parse_percentage
 //   src/genome_stats.rs:4-51                              galah::GenomeAssemblyStats, calculate_genome_stats
+//   src/cluster_validation.rs:7-78                        galah::validate_clusters
+//   src/cluster_validation.rs:80-113                      galah::read_clustering_file
+//   src/cluster_argument_parsing.rs:437-449, :478-484     galah::write_cluster_definition, write_representative_list
 //
 // Errors: the reference panics ("Failed to sketch genomes with finch",
 // src/finch.rs:50); here the same message is thrown as std::runtime_error.
@@ -19,8 +22,10 @@
 #include <charconv>
 #include <cstdint>
 #include <cstdio>
+#include <fstream>
 #include <functional>
 #include <map>
+#include <ostream>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -297,6 +302,141 @@ inline std::vector<std::vector<size_t>> cluster(const std::vector<std::string>& 
     throw std::runtime_error(gg_thread_last_error());
   std::vector<std::vector<size_t>> out(nc);
   for (uint32_t c = 0; c < nc; ++c) out[c].assign(members.begin() + offsets[c], members.begin() + offsets[c + 1]);
+  return out;
+}
+
+// ---- cluster definition files and their validation -------------------------
+
+// src/cluster_argument_parsing.rs:437-449 (--output-cluster-definition): for
+// every cluster, for every genome of it (the representative first, as
+// itself), "<representative>\t<genome>\n".
+inline void write_cluster_definition(std::ostream& f, const std::vector<std::vector<size_t>>& clusters,
+                                     const std::vector<std::string>& genomes) {
+  for (const auto& cluster : clusters)
+    for (size_t g : cluster) f << genomes[cluster[0]] << '\t' << genomes[g] << '\n';
+}
+
+// src/cluster_argument_parsing.rs:478-484 (--output-representative-list)
+inline void write_representative_list(std::ostream& f, const std::vector<std::vector<size_t>>& clusters,
+                                      const std::vector<std::string>& genomes) {
+  for (const auto& cluster : clusters) f << genomes[cluster[0]] << '\n';
+}
+
+// src/cluster_validation.rs:80-113: tab-separated, exactly two fields per
+// line (std::runtime_error otherwise, where the reference exits); a line
+// whose two fields are equal opens a cluster; lines before the first such
+// line are dropped; a member line's first field is not compared with the open
+// representative; empty lines are skipped.  Unlike the reference's csv
+// reader, CSV quoting is not interpreted.
+inline std::vector<std::vector<std::string>> read_clustering_file(const std::string& clustering_file) {
+  std::ifstream in(clustering_file, std::ios::binary);
+  if (!in) throw std::runtime_error("Failed to open clustering file: " + clustering_file);  // :84
+  std::vector<std::vector<std::string>> all_clusters;
+  std::vector<std::string> current_cluster;
+  bool have_rep = false;
+  std::string line;
+  while (std::getline(in, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    const size_t tab = line.find('\t');
+    if (tab == std::string::npos || line.find('\t', tab + 1) != std::string::npos)
+      throw std::runtime_error("Unexpectedly didn't find exactly 2 fields in clustering file: " + line);  // :93-96
+    const std::string first = line.substr(0, tab), second = line.substr(tab + 1);
+    if (first == second) {
+      if (have_rep) all_clusters.push_back(current_cluster);
+      current_cluster.clear();
+      have_rep = true;
+    }
+    current_cluster.push_back(second);
+  }
+  if (have_rep) all_clusters.push_back(current_cluster);
+  return all_clusters;
+}
+
+// galah's error! log: validate_clusters' "not ok" lines.  Replaceable; the
+// default writes to stderr as env_logger would.
+inline std::function<void(const std::string&)>& error_sink() {
+  static std::function<void(const std::string&)> sink = [](const std::string& line) {
+    std::fprintf(stderr, "[ERROR] %s\n", line.c_str());
+  };
+  return sink;
+}
+
+// Rust's `{}` of an f32 (the shortest digits that read back the same value)
+inline std::string rust_f32(float x) {
+  char buf[80];
+  const auto r = std::to_chars(buf, buf + sizeof buf, x, std::chars_format::fixed);
+  return std::string(buf, r.ptr);
+}
+
+// One violation: two paths of the file and the pair's f32 ANI (a fraction).
+struct ClusterViolation {
+  std::string first, second;
+  float ani;
+};
+struct ClusterValidation {
+  uint64_t member_pairs = 0, rep_pairs = 0;
+  std::vector<ClusterViolation> member_bad;  // (representative, member), below the threshold
+  std::vector<ClusterViolation> rep_bad;     // two representatives at or above it
+  bool ok() const { return member_bad.empty() && rep_bad.empty(); }
+};
+
+// src/cluster_validation.rs:7-78 (galah cluster-validate) with finch's ANI in
+// FastANI's place, on the GPU (gg_validate_files): the file is read, every
+// distinct path sketched once, every member checked against its
+// representative (>= ani_threshold, a fraction) and every pair of
+// representatives (< ani_threshold), f32 against f32.  Logs the reference's
+// lines with "finch ANI" for "FastANI" and the values as it prints them
+// (percent: ani * 100 in f32): "Read in {} clusters" to info, the "not ok"
+// lines to error_sink (the "ok" lines of the debug level are not made here).
+inline ClusterValidation validate_clusters(const std::string& clustering_file, float ani_threshold,
+                                           size_t num_kmers = 1000, uint8_t kmer_length = 21,
+                                           const char* sketch_cache_dir = nullptr) {
+  const auto clusters = read_clustering_file(clustering_file);
+  info("Read in " + std::to_string(clusters.size()) + " clusters");  // :17
+  std::map<std::string, uint32_t> index;
+  std::vector<const char*> c_paths;
+  std::vector<uint32_t> members, offsets{0};
+  for (const auto& cluster : clusters) {
+    for (const auto& path : cluster) {
+      auto it = index.find(path);
+      if (it == index.end()) {
+        it = index.emplace(path, (uint32_t)c_paths.size()).first;
+        c_paths.push_back(it->first.c_str());  // (map nodes do not move)
+      }
+      members.push_back(it->second);
+    }
+    offsets.push_back((uint32_t)members.size());
+  }
+  gg_status st = GG_OK;
+  gg_ctx* ctx = gg_create_multi(kmer_length, (uint32_t)num_kmers, 0, nullptr, 0, &st);
+  if (!ctx) throw std::runtime_error(std::string("Failed to sketch genomes with finch: ") + gg_thread_last_error());
+  gg_set_host_threads(ctx, current_num_threads());
+  gg_validation sum{};
+  gg_pair* bad = nullptr;
+  float* bad_ani = nullptr;
+  uint64_t n_bad = 0;
+  st = gg_validate_files(ctx, c_paths.data(), (uint32_t)c_paths.size(), members.data(), offsets.data(),
+                         (uint32_t)clusters.size(), ani_threshold, sketch_cache_dir, &sum, &bad, &bad_ani, &n_bad);
+  if (st != GG_OK) {
+    const std::string msg = gg_last_error(ctx);
+    gg_destroy(ctx);
+    throw std::runtime_error("Failed to sketch genomes with finch: " + msg);  // src/finch.rs:50
+  }
+  gg_destroy(ctx);
+  ClusterValidation out;
+  out.member_pairs = sum.member_pairs;
+  out.rep_pairs = sum.rep_pairs;
+  for (uint64_t p = 0; p < n_bad; ++p) {
+    const ClusterViolation v{c_paths[bad[p].i], c_paths[bad[p].j], bad_ani[p]};
+    const bool member = p < sum.member_bad;
+    (member ? out.member_bad : out.rep_bad).push_back(v);
+    if (error_sink())  // :31-34, :62-65
+      error_sink()(std::string("finch ANI between ") + (member ? "" : "reps ") + v.first + " and " + v.second +
+                   " is not ok: " + rust_f32(v.ani * 100.0f));
+  }
+  gg_free(bad);
+  gg_free(bad_ani);
   return out;
 }
 

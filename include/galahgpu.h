@@ -394,6 +394,74 @@ gg_status gg_cluster_files(gg_ctx* ctx, const char* const* paths, uint32_t n_pat
                            float cluster_ani, const char* cache_dir, uint32_t* rep_of,
                            gg_pair** pairs, float** ani, uint64_t* n_out);
 
+/* ---- ANI of named pairs, cluster validation -------------- */
+/* src/lib.rs:29-37 ClusterDistanceFinder::calculate_ani(fasta1, fasta2) for
+ * a whole list at once: list[p].i and list[p].j name two rows of the sketch
+ * matrix ([n x sketch_size] u64, lens[n], as gg_pairs takes them; rows
+ * ascending without repeats); either orientation, any order, a pair may
+ * repeat, i == j is allowed.  list[p].common and list[p].total receive
+ * finch's merge counts (src/finch.rs:57; an empty row gives 0 and 0, i == j
+ * the row's length twice), whatever the value -- there is no threshold --
+ * and ani[p] (ani may be NULL) gg_ani_f32 of them.  The host-input forms
+ * return GG_ERR_INVALID_ARG for an index >= n, lens[g] > sketch_size or
+ * m >= 2^31. */
+
+/* On the host (the merge itself); no device, no ctx. */
+gg_status gg_ani_pairs_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                            int kmer_length, gg_pair* list, uint64_t m, float* ani);
+/* The same on the context's (first) device: host arrays in and out, one
+ * kernel launch per list. */
+gg_status gg_ani_pairs(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n, gg_pair* list,
+                       uint64_t m, float* ani);
+/* Device-resident: the integers only (gg_ani_f32 is host arithmetic), on the
+ * given stream, asynchronous.  The input is not checked: an entry with an
+ * index >= n is never followed and receives 0 and 0; a length above the
+ * context's sketch size is read as the sketch size. */
+gg_status gg_ani_pairs_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                              gg_pair* d_list, uint64_t m, void* stream);
+
+/* src/cluster_validation.rs:7-78 validate_clusters with finch's ANI in the
+ * place of FastANI.  clusters in gg_clusters_from_reps' CSR form (cluster c
+ * is members[offsets[c] .. offsets[c+1]), its representative first; a genome
+ * may occur more than once), ani the threshold as an f32 fraction; both
+ * comparisons are f32 against f32 on gg_ani_f32 of the pair.
+ *   :21-45  every listed genome other than its cluster's representative: bad
+ *           iff its value to the representative < ani (the reference also
+ *           compares the representative with itself; that pair is neither
+ *           made nor counted);
+ *   :47-77  every pair of clusters' representatives: bad iff >= ani (finch
+ *           always yields a value: the "too divergent" arm never fires).
+ * *bad (gg_free) holds the member violations as (representative, member),
+ * sorted so, one per listing, then the representative violations as
+ * (r1 < r2), sorted (r1 == r2 when one genome heads two clusters), with
+ * common and total set; *bad_ani (gg_free) their f32.  sum->rep_pairs is
+ * R (R - 1) / 2 for R clusters.  GG_ERR_INVALID_ARG for an index >= n,
+ * lens[g] > sketch_size, a NaN ani, an empty cluster, offsets that do not
+ * ascend, or 2^31 listed genomes or more. */
+typedef struct gg_validation {
+  uint64_t member_pairs;
+  uint64_t member_bad;
+  uint64_t rep_pairs;
+  uint64_t rep_bad;
+} gg_validation;
+
+/* On the host: N + R (R - 1) / 2 merges; no device, no ctx. */
+gg_status gg_validate_clusters_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                                    int kmer_length, const uint32_t* members, const uint32_t* offsets,
+                                    uint32_t n_clusters, float ani, gg_validation* sum, gg_pair** bad,
+                                    float** bad_ani, uint64_t* n_bad);
+/* On the device: the members as one named list (first member of a
+ * multi-device context), the representatives' rows through the all-pairs
+ * path of gg_pairs at a threshold that keeps a superset, then the f32 rule. */
+gg_status gg_validate_clusters(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                               const uint32_t* members, const uint32_t* offsets, uint32_t n_clusters, float ani,
+                               gg_validation* sum, gg_pair** bad, float** bad_ani, uint64_t* n_bad);
+/* gg_sketch_files(paths, cache_dir) followed by gg_validate_clusters over
+ * its rows: members index paths. */
+gg_status gg_validate_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, const uint32_t* members,
+                            const uint32_t* offsets, uint32_t n_clusters, float ani, const char* cache_dir,
+                            gg_validation* sum, gg_pair** bad, float** bad_ani, uint64_t* n_bad);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);
@@ -421,11 +489,12 @@ void gg_free(void* p);
  * the first; gg_sketch_files_stats adds its two statistics passes to them)
  * and the PCIe upload of each staged batch (bytes).  GG_KERNEL_CLUSTER is
  * every kernel of gg_cluster_pairs(_device) (work: pairs, counted on the
- * first). */
+ * first).  GG_KERNEL_ANI_PAIRS is the named-pair kernel of gg_ani_pairs(_device)
+ * and gg_validate_clusters (work: listed pairs). */
 enum { GG_KERNEL_SKETCH = 0, GG_KERNEL_FINALIZE = 1, GG_KERNEL_PAIRS = 2, GG_KERNEL_PAIRS_INDEX = 3,
        GG_KERNEL_INFLATE_SEARCH = 4, GG_KERNEL_INFLATE_DECODE = 5, GG_KERNEL_INFLATE_EXPAND = 6,
        GG_KERNEL_INFLATE_RESOLVE = 7, GG_KERNEL_INFLATE_CRC = 8, GG_KERNEL_PARSE = 9, GG_KERNEL_UPLOAD = 10,
-       GG_KERNEL_CLUSTER = 11, GG_KERNEL_COUNT = 12 };
+       GG_KERNEL_CLUSTER = 11, GG_KERNEL_ANI_PAIRS = 12, GG_KERNEL_COUNT = 13 };
 typedef struct gg_kernel_stats {
   double ms;
   uint64_t launches;

@@ -50,7 +50,8 @@ pub const GG_KERNEL_INFLATE_CRC: c_int = 8;
 pub const GG_KERNEL_PARSE: c_int = 9;
 pub const GG_KERNEL_UPLOAD: c_int = 10;
 pub const GG_KERNEL_CLUSTER: c_int = 11;
-pub const GG_KERNEL_COUNT: c_int = 12;
+pub const GG_KERNEL_ANI_PAIRS: c_int = 12;
+pub const GG_KERNEL_COUNT: c_int = 13;
 
 pub const GG_PATH_INDEX: c_int = 0;
 pub const GG_PATH_INDEX_ABANDONED: c_int = 1;
@@ -143,6 +144,17 @@ pub struct gg_genome_stats {
     pub num_ambiguous_bases: u64,
     pub n50: u64,
     pub total_bases: u64,
+}
+
+/// The counts of a cluster validation (`gg_validation`;
+/// src/cluster_validation.rs:21-45 members, :47-77 representatives).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gg_validation {
+    pub member_pairs: u64,
+    pub member_bad: u64,
+    pub rep_pairs: u64,
+    pub rep_bad: u64,
 }
 
 /// `gg_pair_sink`: a block of compared pairs; return 0 to go on.
@@ -239,6 +251,26 @@ extern "C" {
     pub fn gg_cluster_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
                             cluster_ani: f32, cache_dir: *const c_char, rep_of: *mut u32, pairs: *mut *mut gg_pair,
                             ani: *mut *mut f32, n_out: *mut u64) -> GgStatus;
+
+    // ANI of named pairs (src/lib.rs:29-37), cluster validation (src/cluster_validation.rs:7-78)
+    pub fn gg_ani_pairs_host(sketches: *const u64, lens: *const u32, n: u32, sketch_size: u32, kmer_length: c_int,
+                             list: *mut gg_pair, m: u64, ani: *mut f32) -> GgStatus;
+    pub fn gg_ani_pairs(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, list: *mut gg_pair, m: u64,
+                        ani: *mut f32) -> GgStatus;
+    pub fn gg_ani_pairs_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32,
+                               d_list: *mut gg_pair, m: u64, stream: *mut c_void) -> GgStatus;
+    pub fn gg_validate_clusters_host(sketches: *const u64, lens: *const u32, n: u32, sketch_size: u32,
+                                     kmer_length: c_int, members: *const u32, offsets: *const u32, n_clusters: u32,
+                                     ani: f32, sum: *mut gg_validation, bad: *mut *mut gg_pair,
+                                     bad_ani: *mut *mut f32, n_bad: *mut u64) -> GgStatus;
+    pub fn gg_validate_clusters(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32,
+                                members: *const u32, offsets: *const u32, n_clusters: u32, ani: f32,
+                                sum: *mut gg_validation, bad: *mut *mut gg_pair, bad_ani: *mut *mut f32,
+                                n_bad: *mut u64) -> GgStatus;
+    pub fn gg_validate_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, members: *const u32,
+                             offsets: *const u32, n_clusters: u32, ani: f32, cache_dir: *const c_char,
+                             sum: *mut gg_validation, bad: *mut *mut gg_pair, bad_ani: *mut *mut f32,
+                             n_bad: *mut u64) -> GgStatus;
 
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;
