@@ -14,7 +14,10 @@
 //     window at its start and that window's reverse complement once, and
 //     takes every k-mer's forward and reverse-complement codes as static
 //     64-bit slices of the two (the canonical code is a 64-bit min).  Each
-//     workgroup sweeps a contiguous chunk of segments.
+//     workgroup sweeps a contiguous chunk of segments, a lane two consecutive
+//     ones per visit.  A lane carries its place in the run from window to
+//     window (word pointer, base offset, k-mers left, tau and slot) and goes
+//     back to the run index only when a window falls in another run.
 //   * The first multiply of each murmur3 input word, the rotates and the
 //     second multiply of the k1 and k2 words, and the whole tail word are
 //     folded into LDS tables indexed by 8-bit groups of 4 bases (see
@@ -50,6 +53,17 @@ constexpr int kBlock = 256;
 #ifndef GG_K1_MIN_WAVES
 #define GG_K1_MIN_WAVES 7
 #endif
+// Consecutive segments a lane hashes per visit (a stretch).  Inside a run a
+// window follows from the lane's last one whatever the distance, so on long
+// runs the stretch changes nothing (C3: 1, 2 and 4 within each other's
+// spread); on C5's 10 kb runs, where a lane's next visit is in another run,
+// 2 and 4 save the run search for the windows inside a stretch (K1 57.03 /
+// 57.08 ms against 57.47 at 1 and 57.70 before; profiles/k1_stretch/).
+#ifndef GG_K1_STRETCH
+#define GG_K1_STRETCH 2
+#endif
+constexpr int kStretch = GG_K1_STRETCH;
+static_assert(kStretch >= 1 && kStretch <= 16, "stretch");
 
 // 64-bit rotate left by a compile-time amount as two v_alignbit_b32
 // (hipcc otherwise emits a 64-bit shift + shift + or).
@@ -481,14 +495,16 @@ __global__ __launch_bounds__(kBlock, GG_K1_MIN_WAVES) void sketch_candidates_ker
   __shared__ __attribute__((aligned(16))) uint64_t mtab[HashShape<K>::TAB_U64];  // murmur word tables (hash_parts)
   __shared__ CandQueue queues[kBlock / 64];
   CandQueue& q = queues[threadIdx.x >> 6];
-  // Workgroup b sweeps its own contiguous chunk of segments, kBlock at a
-  // time (a wave's 64 lanes read consecutive windows).  A lane's next
-  // segment is then kBlock segments on, in the same run or a few runs later,
-  // so find_run's forward search is one or two loads; with a grid stride
-  // it was ~50 genomes on (C3: ~14 dependent loads per segment, C5's 3.6M
-  // runs ~30).
+  // Workgroup b sweeps its own contiguous chunk of segments, kBlock * kStretch
+  // at a time: in visit v lane t takes segments c0 + (v * kBlock + t) *
+  // kStretch + j, j < kStretch (a wave's 64 lanes read neighbouring
+  // stretches).  A lane's next stretch is then kBlock stretches on, in the
+  // same run or a few runs later, so find_run's forward search is one or two
+  // loads; with a grid stride it was ~50 genomes on (C3: ~14 dependent loads
+  // per segment, C5's 3.6M runs ~30).
   const uint64_t n_segs = a.n_segs_dev ? *a.n_segs_dev : a.n_segs;
-  const uint64_t per_wg = (n_segs + (uint64_t)gridDim.x * kBlock - 1) / ((uint64_t)gridDim.x * kBlock) * kBlock;
+  constexpr uint64_t kVisit = (uint64_t)kBlock * kStretch;  // segments of one visit of the workgroup
+  const uint64_t per_wg = (n_segs + (uint64_t)gridDim.x * kVisit - 1) / ((uint64_t)gridDim.x * kVisit) * kVisit;
   const uint64_t c0 = a.seg0 + (uint64_t)blockIdx.x * per_wg;
   const uint64_t send = min(a.seg0 + n_segs, c0 + per_wg);
   if (c0 >= send) return;  // (uniform) no segment for this workgroup
@@ -507,26 +523,61 @@ __global__ __launch_bounds__(kBlock, GG_K1_MIN_WAVES) void sketch_candidates_ker
     });
   };
 
-  for (uint64_t sg = c0 + threadIdx.x; sg < send; sg += kBlock) {
-    r = find_run(a.run_sstart, a.n_runs, sg, r);
-    const gg_run run = a.runs[r];
-    const uint32_t k0 = (uint32_t)(sg - a.run_sstart[r]) * (uint32_t)kSeg;  // first k-mer of the segment in the run
-    const uint32_t cnt = min((uint32_t)kSeg, run.len - (uint32_t)K + 1u - k0);
-    const uint32_t slot = run.genome - a.slot_genome0;
-    const uint64_t tau = a.tau[slot];
-    // prefilter on the high words: h = fmix_last(f1) + fmix_last(f2)
-    // has high word S or S + 1 (carry), S = hi(f1) + hi(f2), so h <= tau
-    // needs S <= hi(tau) or S = 2^32 - 1, i.e. S + 1 <= hi(tau) + 1 (mod
-    // 2^32; every S passes when hi(tau) = 2^32 - 1)
-    const uint32_t tau_hi = (uint32_t)(tau >> 32);
-    const uint32_t thr = tau_hi == 0xFFFFFFFFu ? 0xFFFFFFFFu : tau_hi + 1u;
-    const uint64_t b = run.base + k0;  // first base of the segment's first k-mer
-
-    const uint64_t wi = b >> 4;
-    const uint32_t off = (uint32_t)b & 15u;
+  // A lane's state between windows: everything the next window needs that
+  // the run table, the segment index and tau would otherwise be read for
+  // again.  The next window is `d` segments on (1 inside a stretch, to the
+  // lane's next stretch otherwise); while that stays inside the run (the run
+  // has more than d * kSeg k-mers from this window's first) the window's
+  // base, its k-mer count and the run's tau and slot follow from the state,
+  // and only a window in another run searches the run index and loads its
+  // run, tau and slot.
+  const uint32_t* const wend = a.words + a.n_words;
+  const uint32_t* wp = a.words;  // the word holding the window's first base
+  uint32_t off = 0;              // the base's place in it
+  uint32_t rem = 0;              // k-mers of the run from the window's first (0: no window yet)
+  uint32_t slot = 0, thr = 0;
+  uint64_t tau = 0;
+  uint32_t win = 0;              // window of the stretch (uniform)
+  uint32_t d = 0;                // segments since the lane's last window
+  // the window's segment is c0 + rel (a workgroup's chunk is far below 2^32 segments)
+  const uint32_t nrel = (uint32_t)(send - c0);
+  uint32_t rel = threadIdx.x * (uint32_t)kStretch;
+#pragma nounroll
+  while (rel < nrel) {
+    if (d * (uint32_t)kSeg >= rem) {  // (divergent, rare) another run
+      const uint64_t sg = c0 + rel;
+      r = find_run(a.run_sstart, a.n_runs, sg, r);
+      const gg_run run = a.runs[r];
+      const uint32_t k0 = (uint32_t)(sg - a.run_sstart[r]) * (uint32_t)kSeg;  // first k-mer of the segment in the run
+      rem = run.len - (uint32_t)K + 1u - k0;
+      slot = run.genome - a.slot_genome0;
+      tau = a.tau[slot];
+      // prefilter on the high words: h = fmix_last(f1) + fmix_last(f2)
+      // has high word S or S + 1 (carry), S = hi(f1) + hi(f2), so h <= tau
+      // needs S <= hi(tau) or S = 2^32 - 1, i.e. S + 1 <= hi(tau) + 1 (mod
+      // 2^32; every S passes when hi(tau) = 2^32 - 1)
+      const uint32_t tau_hi = (uint32_t)(tau >> 32);
+      thr = tau_hi == 0xFFFFFFFFu ? 0xFFFFFFFFu : tau_hi + 1u;
+      const uint64_t b = run.base + k0;  // first base of the segment's first k-mer
+      wp = a.words + (b >> 4);
+      off = (uint32_t)b & 15u;
+    } else {  // d segments on in the same run
+      rem -= d * (uint32_t)kSeg;
+      const uint32_t t = off + d * (uint32_t)kSeg;
+      wp += t >> 4;
+      off = t & 15u;
+    }
+    const uint32_t cnt = min((uint32_t)kSeg, rem);
+    // the window's five words: one check that the last lies inside the
+    // buffer; the window at the buffer's end reads the words past it as 0
     uint32_t w[5];
+    if (wp + 4 < wend) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) w[j] = (wi + j < a.n_words) ? a.words[wi + j] : 0u;
+      for (int i = 0; i < 5; ++i) w[i] = wp[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) w[i] = (wp + i < wend) ? wp[i] : 0u;
+    }
     uint32_t F[4], R[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -570,6 +621,13 @@ __global__ __launch_bounds__(kBlock, GG_K1_MIN_WAVES) void sketch_candidates_ker
       }
     }
     drain(kQueueDrain);
+    // the stretch's next window, or the first of the lane's next stretch
+    d = 1u;
+    if (++win == (uint32_t)kStretch) {
+      win = 0;
+      d += (uint32_t)((kBlock - 1) * kStretch);
+    }
+    rel += d;
   }
   drain(1);  // every lane of the wave is back
 }
