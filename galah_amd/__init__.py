@@ -37,6 +37,7 @@ __all__ = [
     "cluster_pairs_host", "clusters_from_reps", "ClusterDistanceFinder", "FinchClusterer", "cluster",
     "ani_pairs_host", "validate_clusters_host", "Validation", "ClusterValidation", "validate_clusters",
     "read_clustering_file", "write_cluster_definition", "write_representative_list",
+    "pairs_border_host", "PreclusterState", "relabel_pairs", "cluster_update",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "gg_cluster_pairs_host", "gg_cluster_pairs", "gg_cluster_pairs_device", "gg_clusters_from_reps", "gg_cluster_files",
     "gg_ani_pairs_host", "gg_ani_pairs", "gg_ani_pairs_device",
     "gg_validate_clusters_host", "gg_validate_clusters", "gg_validate_files",
+    "gg_pairs_border", "gg_pairs_border_device", "gg_pairs_border_host", "gg_update_files",
 )
 
 GG_OK = 0
@@ -144,6 +146,13 @@ _sig("gg_pair_tiles", _u64, [_u32])
 _sig("gg_pair_partition", None, [_u32, _u32, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64)])
 _sig("gg_pairs", _i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
 _sig("gg_pairs_device", _i32, [_vp, _vp, _vp, _u32, _u64, _u64, ctypes.c_float, _vp, _u64, _vp, _vp])
+_sig("gg_pairs_border", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_pairs_border_device", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, _vp, _u64, _vp, _vp])
+_sig("gg_pairs_border_host", _i32, [_vp, _vp, _u32, _u32, _u32, _i32, ctypes.c_float, ctypes.POINTER(_vp),
+                                    ctypes.POINTER(_u64)])
+_sig("gg_update_files", _i32, [_vp, _vp, _vp, _u32, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
+                               ctypes.c_char_p, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                               ctypes.POINTER(_u64)])
 _sig("gg_precluster_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
 _sig("gg_precluster_files_cached", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
@@ -455,6 +464,20 @@ def ani_pairs_host(sketches, lens, pairs, k=21):
     if st != GG_OK:
         raise _thread_err(st)
     return p, ani[:len(p)]
+
+
+def pairs_border_host(sketches, lens, n_old, min_ani, k=21):
+    """The border of a sketch matrix on the host (gg_pairs_border_host, no
+    device): every passing pair (i < j) with j >= n_old, sorted by (i, j), so
+    that pairs(rows) == pairs(rows[:n_old]) + pairs_border(rows, n_old) as
+    sets.  n_old == 0 gives every pair, n_old == n none."""
+    sk, ln, n, s = _rows_arg(sketches, lens)
+    outp, cnt = _vp(), _u64()
+    st = _L.gg_pairs_border_host(_ptr(sk), _ptr(ln), n, int(n_old), s, int(k), ctypes.c_float(min_ani),
+                                 ctypes.byref(outp), ctypes.byref(cnt))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return _take_pairs(outp, cnt.value)
 
 
 def validate_clusters_host(sketches, lens, clusters, ani, k=21):
@@ -891,6 +914,39 @@ class Context:
             raise self._err(st)
         return _take_pairs(outp, cnt.value)
 
+    def pairs_border(self, sketches, lens, n_old, min_ani):
+        """The border of a sketch matrix (gg_pairs_border): the passing pairs
+        (i < j) with j >= n_old, sorted by (i, j) -- what rows [n_old, n) add
+        to pairs(sketches[:n_old]).  On the context's (first) device; only the
+        new rows are evaluated."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        outp, cnt = _vp(), _u64()
+        st = _L.gg_pairs_border(self._c, _ptr(sk), _ptr(ln), n, int(n_old), ctypes.c_float(min_ani),
+                                ctypes.byref(outp), ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        return _take_pairs(outp, cnt.value)
+
+    def update_files(self, old_sketches, old_lens, new_paths, min_ani, cache_dir=None):
+        """A finished run carried forward (gg_update_files): only new_paths are
+        read and sketched (cache_dir as sketch_files), placed after the old
+        rows, and the border evaluated -> (new sketches [n_new, s], new lens,
+        border pairs sorted by (i, j) with indices into old + new, their f32
+        ANI)."""
+        sk, ln, n_old, _ = _rows_arg(old_sketches, old_lens, self.s)
+        n_new = len(new_paths)
+        arr = (ctypes.c_char_p * max(n_new, 1))(*[os.fsencode(p) for p in new_paths])
+        out = np.zeros((max(n_new, 1), self.s), dtype=np.uint64)
+        lens = np.zeros(max(n_new, 1), dtype=np.uint32)
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        st = _L.gg_update_files(self._c, _ptr(sk), _ptr(ln), n_old, arr, n_new, ctypes.c_float(min_ani),
+                                None if cache_dir is None else os.fsencode(cache_dir), _ptr(out), _ptr(lens),
+                                ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
+        return out[:n_new], lens[:n_new], pairs, ani
+
     def sketch_files(self, paths, cache_dir=None):
         """finch sketch_files (src/finch.rs:47) for files -> (sketches [n, s] u64
         padded with 0, lens [n] u32, number of genomes served by cache_dir)."""
@@ -1049,6 +1105,18 @@ class Context:
         st = _L.gg_pairs_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, tile_begin, tile_end,
                                 ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
                                 None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+
+    def pairs_border_device(self, d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count, stream=None):
+        """pairs_border over device-resident tensors, the contract of
+        pairs_device (appends unsorted to d_out, d_count incremented by the
+        number found, entries past out_cap dropped; asynchronous).  d_sketches
+        may be a tensor with spare rows kept between updates: a batch of new
+        sketches is written after the n_old rows it holds and only n grows."""
+        st = _L.gg_pairs_border_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, int(n_old),
+                                       ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
+                                       None if stream is None else stream)
         if st != GG_OK:
             raise self._err(st)
 
@@ -1278,6 +1346,137 @@ class FinchPreclusterer(PreclusterDistanceFinder):
 
     def method_name(self):
         return "finch"
+
+    def distances_state(self, genome_fasta_paths):
+        """distances() that can be carried forward: a PreclusterState of the
+        paths, their sketches and the passing pairs (state.cache() is what
+        distances() returns)."""
+        empty = PreclusterState([], np.zeros((0, self.num_kmers), np.uint64), np.zeros(0, np.uint32),
+                                np.zeros(0, PAIR_DTYPE), np.zeros(0, np.float32), self.kmer_length, self.num_kmers, 0,
+                                self.min_ani)
+        return self.update(empty, genome_fasta_paths)
+
+    def update(self, state, new_paths):
+        """Adds genomes to a finished run -> a PreclusterState over state.paths
+        + new_paths whose cache() equals distances(state.paths + new_paths):
+        only the new files are read and sketched, and only the pairs that
+        involve a new genome are evaluated (Context.update_files).  ValueError
+        when the state was made with another k, sketch size, seed or min_ani,
+        or when a new path is already present."""
+        new_paths = [os.fspath(p) for p in new_paths]
+        mine = (self.kmer_length, self.num_kmers, 0, np.float32(self.min_ani).tobytes())
+        if (state.k, state.s, state.seed, np.float32(state.min_ani).tobytes()) != mine:
+            raise ValueError("PreclusterState of k=%d s=%d seed=%d min_ani=%r, preclusterer of k=%d s=%d seed=0 "
+                             "min_ani=%r" % (state.k, state.s, state.seed, state.min_ani, self.kmer_length,
+                                             self.num_kmers, self.min_ani))
+        seen = set(state.paths)
+        for p in new_paths:
+            if p in seen:
+                raise ValueError("genome already present: %s" % p)
+            seen.add(p)
+        try:
+            ctx = _context(self.kmer_length, self.num_kmers)
+            sk, lens, border, border_ani = ctx.update_files(state.sketches, state.lens, new_paths,
+                                                            float(self.min_ani), cache_dir=self.sketch_cache_dir)
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+        pairs = np.concatenate([state.pairs, border])
+        ani = np.concatenate([state.ani, border_ani])
+        by_ij = np.lexsort((pairs["j"], pairs["i"]))  # SortedPairGenomeDistanceCache order
+        return PreclusterState(state.paths + new_paths, np.concatenate([state.sketches, sk]),
+                               np.concatenate([state.lens, lens]), pairs[by_ij], ani[by_ij], state.k, state.s,
+                               state.seed, state.min_ani)
+
+
+class PreclusterState:
+    """A finished precluster run that genomes can be added to: the paths, their
+    sketches [n, s] u64 and lens [n] u32, the passing pairs (PAIR_DTYPE, sorted
+    by (i, j)) with their f32 ANI, and the parameters they were made with (k,
+    s, seed, min_ani).  FinchPreclusterer.distances_state makes one,
+    FinchPreclusterer.update carries it forward."""
+
+    def __init__(self, paths, sketches, lens, pairs, ani, k, s, seed, min_ani):
+        self.paths = [os.fspath(p) for p in paths]
+        self.sketches = np.ascontiguousarray(sketches, dtype=np.uint64).reshape(len(self.paths), int(s))
+        self.lens = np.ascontiguousarray(lens, dtype=np.uint32).reshape(len(self.paths))
+        self.pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE).reshape(-1)
+        self.ani = np.ascontiguousarray(ani, dtype=np.float32).reshape(len(self.pairs))
+        self.k, self.s, self.seed, self.min_ani = int(k), int(s), int(seed), np.float32(min_ani)
+
+    def cache(self):
+        """The pairs as FinchPreclusterer.distances returns them."""
+        cache = SortedPairGenomeDistanceCache()
+        for p, a in zip(self.pairs, self.ani):
+            cache.insert((int(p["i"]), int(p["j"])), np.float32(a))
+        return cache
+
+    def save(self, file):
+        """One .npz of plain arrays (no pickled objects): a path or a binary
+        file object.  Paths are stored as their file-system bytes."""
+        raw = [os.fsencode(p) for p in self.paths]
+        ends = np.cumsum([len(b) for b in raw], dtype=np.uint64) if raw else np.zeros(0, np.uint64)
+        quads = np.stack([self.pairs[f] for f in ("i", "j", "common", "total")], axis=1).astype(np.uint32)
+        np.savez(file, path_bytes=np.frombuffer(b"".join(raw), dtype=np.uint8), path_ends=ends,
+                 sketches=self.sketches, lens=self.lens, pairs=quads.reshape(-1, 4), ani=self.ani,
+                 params=np.array([self.k, self.s, self.seed], dtype=np.uint64),
+                 min_ani=np.array([self.min_ani], dtype=np.float32))
+
+    @classmethod
+    def load(cls, file):
+        with np.load(file, allow_pickle=False) as z:
+            blob, ends = z["path_bytes"].tobytes(), z["path_ends"].astype(np.int64)
+            starts = np.concatenate([[0], ends[:-1]]) if len(ends) else ends
+            paths = [os.fsdecode(blob[a:b]) for a, b in zip(starts, ends)]
+            quads = z["pairs"].reshape(-1, 4)
+            pairs = np.zeros(len(quads), dtype=PAIR_DTYPE)
+            for x, f in enumerate(("i", "j", "common", "total")):
+                pairs[f] = quads[:, x]
+            k, s, seed = (int(v) for v in z["params"])
+            return cls(paths, z["sketches"], z["lens"], pairs, z["ani"], k, s, seed, z["min_ani"][0])
+
+
+def relabel_pairs(pairs, order):
+    """The pairs of genomes numbered 0 .. n-1 renumbered by position in
+    `order` (a permutation: position -> genome); i and j keep their places in
+    each record, so a record may come out with i > j (cluster_pairs takes
+    either orientation)."""
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    n = len(order)
+    if n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n):
+        raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
+    pos = np.empty(n, dtype=np.uint32)
+    pos[order] = np.arange(n, dtype=np.uint32)
+    out = np.array(pairs, dtype=PAIR_DTYPE).reshape(-1)
+    if len(out) and (int(out["i"].max()) >= n or int(out["j"].max()) >= n):
+        raise ValueError("pair index out of range of order")
+    out["i"], out["j"] = pos[out["i"]], pos[out["j"]]
+    return out
+
+
+def cluster_update(state, new_paths, preclusterer, clusterer, order=None):
+    """Adds new_paths to a finished run and clusters the union -> (clusters,
+    new_state): preclusterer.update(state, new_paths), then the union's pairs
+    relabelled through `order` and clustered on the device as cluster() does.
+    order is a permutation of the union, position -> index into state.paths +
+    new_paths (galah clusters in the order it is given: quality order); the
+    default is the old genomes in their order, then the new ones as given, so
+    that old representatives keep precedence.  clusters are lists of positions
+    in that order, each with its representative first: what
+    cluster([paths[g] for g in order], ...) returns."""
+    clusterer.initialise()
+    pre_name, clu_name = preclusterer.method_name(), clusterer.method_name()
+    if not (pre_name == clu_name == "finch"):
+        raise NotImplementedError("galah_amd.cluster_update: only finch + finch runs here, not %s + %s"
+                                  % (pre_name, clu_name))
+    new_state = preclusterer.update(state, new_paths)
+    n = len(new_state.paths)
+    pairs = relabel_pairs(new_state.pairs, np.arange(n) if order is None else order)
+    try:
+        rep_of = _context(preclusterer.kmer_length, preclusterer.num_kmers).cluster_pairs(
+            n, pairs, new_state.ani, float(np.float32(clusterer.get_ani_threshold())))
+    except GalahGpuError as e:
+        raise RuntimeError("Failed to cluster genomes: %s" % e) from e
+    return clusters_from_reps(rep_of), new_state
 
 
 class ClusterDistanceFinder:

@@ -689,7 +689,10 @@ void build_segments(std::vector<PairSeg>& segs, uint64_t nb, uint64_t tb, uint64
 // same columns through its L2.
 gg_status pairs_gate(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, uint64_t nb,
                      uint64_t tb, uint64_t te, const uint32_t* d_cmin, const uint32_t* d_sufmin, gg_pair* d_out,
-                     uint64_t cap, uint64_t* d_count, uint64_t work, hipStream_t st) {
+                     uint64_t cap, uint64_t* d_count, uint64_t work, hipStream_t st, uint32_t n_old = 0) {
+  // (n_old > 0, the border form: of every tile row only the column tiles
+  // that hold a row >= n_old, the columns below n_old skipped by the kernel;
+  // the tables cover every tile row)
   constexpr uint32_t kGateXcdRun = 64;  // ~ workgroups resident per XCD (32 CUs x 2)
   const GateParams gp = gate_params(c->s);
   if (gp.cap > 65535u || c->s > kMaxSketch)
@@ -705,7 +708,7 @@ gg_status pairs_gate(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, ui
       if (lo >= hi) continue;
       I0 = std::min<uint32_t>(I0, (uint32_t)I);
       I1 = std::max<uint32_t>(I1, (uint32_t)I);
-      uint64_t J = I + (lo - first);
+      uint64_t J = std::max<uint64_t>(I + (lo - first), n_old / GG_PAIR_TILE);
       const uint64_t Jend = I + (hi - first);
       while (J < Jend) {
         const uint64_t Jn = std::min<uint64_t>(Jend, (J / kGateSegTiles + 1) * kGateSegTiles);
@@ -761,6 +764,7 @@ gg_status pairs_gate(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, ui
   g.out = d_out;
   g.out_cap = cap;
   g.count = (unsigned long long*)d_count;
+  g.col_min = n_old;
   GG_HIP(c, timed_launch(c, GG_KERNEL_PAIRS, work, st, [&] {
     hipError_t e = launch_gate_build(bl, st);
     return e != hipSuccess ? e : launch_pairs_gate(g, st);
@@ -777,7 +781,9 @@ gg_status pairs_gate(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, ui
 gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, uint64_t nb,
                       uint64_t tb, uint64_t te, const uint32_t* d_cmin, const uint32_t* d_sufmin, gg_pair* d_out,
                       uint64_t cap, uint64_t* d_count, uint64_t work, hipStream_t st, bool* used, bool* costly,
-                      bool weigh_cost) {
+                      bool weigh_cost, uint32_t n_old = 0) {
+  // (n_old > 0, the border form over every tile: the pairs kernel takes rows
+  // [n_old, n), each against the rows before it)
   // (runs in row order -- every build but the row-range one -- read only the
   // members after each entry; a longer run's start is found by walks that
   // grow with it, so past this the gate kernel runs instead)
@@ -823,14 +829,16 @@ gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, u
     *used = true;
     return GG_OK;
   }
-  const uint32_t r0 = (uint32_t)(I0 * GG_PAIR_TILE), r1 = (uint32_t)std::min<uint64_t>(n, I1 * GG_PAIR_TILE);
+  const uint32_t r0 = n_old ? n_old : (uint32_t)(I0 * GG_PAIR_TILE);
+  const uint32_t r1 = n_old ? n : (uint32_t)std::min<uint64_t>(n, I1 * GG_PAIR_TILE);
+  b.border = n_old != 0;
+  b.border0 = n_old;
   // A device that evaluates only some rows (a multi-device call) indexes only
   // the entries whose hash may occur in them (GALAHGPU_INDEX_RANGE=0: every
-  // entry, as a single device does).
-  static const bool range_on = [] {
-    const char* e = getenv("GALAHGPU_INDEX_RANGE");
-    return !(e && *e == '0');
-  }();
+  // entry, as a single device does).  The border form has such a range too:
+  // the new rows.  (Read per call, as the other index knobs are.)
+  const char* re = getenv("GALAHGPU_INDEX_RANGE");
+  const bool range_on = !(re && *re == '0');
   // (a range of more than ~40% of the rows keeps most entries anyway: the
   // filter would cost more than the smaller sort saves)
   if (range_on && (r0 > 0 || r1 < n) && 5ull * (r1 - r0) <= 2ull * n) {
@@ -869,6 +877,7 @@ gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, u
   a.out = d_out;
   a.out_cap = cap;
   a.count = (unsigned long long*)d_count;
+  a.border = n_old != 0;
   // GALAHGPU_INDEX_MAX_SPLIT (tests): fewer partner classes per row, so the
   // overflow fallback below can be reached on small inputs
   {
@@ -890,7 +899,10 @@ gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, u
     const char* e = getenv("GALAHGPU_INDEX_COST");
     const double k = !weigh_cost ? 0.0 : e && *e ? atof(e) : 0.0;
     // (a member of a multi-device call weighs its share: the pairs of its tiles)
-    const double lim = k * (double)c->s * (double)pairs_in_tiles(n, tb, te);
+    // (the border form: the pairs that involve a new row)
+    const uint64_t n_new = n - n_old;
+    const uint64_t npairs = n_old ? n_new * n_old + n_new * (n_new - 1) / 2 : pairs_in_tiles(n, tb, te);
+    const double lim = k * (double)c->s * (double)npairs;
     a.cost = b.cost;
     a.cost_limit = k > 0 && lim < 1.8e19 ? (unsigned long long)lim : ~0ull;
   }
@@ -1020,13 +1032,18 @@ gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, u
 
 gg_status pairs_core(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                      uint64_t tb, uint64_t te, float min_ani, gg_pair* d_out, uint64_t cap,
-                     uint64_t* d_count, hipStream_t st) {
+                     uint64_t* d_count, hipStream_t st, uint32_t n_old) {
   uint32_t *d_cmin, *d_sufmin;
   gg_status cs = ensure_cmin(c, min_ani, &d_cmin, &d_sufmin, st);
   if (cs != GG_OK) return cs;
   const uint64_t nb = (n + GG_PAIR_TILE - 1) / GG_PAIR_TILE;
   te = std::min<uint64_t>(te, gg_pair_tiles(n));
-  const uint64_t work = c->timing ? pairs_in_tiles(n, tb, te) : 0;
+  if (n_old) {  // the border: every tile, the pairs with j >= n_old (n_old < n: the caller's)
+    tb = 0;
+    te = gg_pair_tiles(n);
+  }
+  const uint64_t n_new = n - std::min(n, n_old);
+  const uint64_t work = !c->timing ? 0 : n_old ? n_new * n_old + n_new * (n_new - 1) / 2 : pairs_in_tiles(n, tb, te);
 #if defined(GG_XCHECK)
   int kern = (c->pairs_kernel == 1 && pairs_table_rows(c->s) == 0) ? 2 : c->pairs_kernel;
 #else
@@ -1048,7 +1065,7 @@ gg_status pairs_core(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, ui
     if (c->sufmin_host[0] != 0 && fits && n >= 2 && (kern == 4 || n >= 512)) {
       bool used = false, costly = false;
       gg_status is = pairs_index(c, d_sk, d_lens, n, nb, tb, te, d_cmin, d_sufmin, d_out, cap, d_count, work, st,
-                                 &used, &costly, kern == 0);
+                                 &used, &costly, kern == 0, n_old);
       if (is != GG_OK) return is;
       ++c->pair_paths[used ? GG_PATH_INDEX : GG_PATH_INDEX_ABANDONED];
       if (costly) ++c->index_costly;
@@ -1058,8 +1075,9 @@ gg_status pairs_core(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, ui
   }
   ++c->pair_paths[(kern == 0 || kern == 3) ? GG_PATH_GATE : GG_PATH_OTHER];
   if (kern == 0 || kern == 3)
-    return pairs_gate(c, d_sk, d_lens, n, nb, tb, te, d_cmin, d_sufmin, d_out, cap, d_count, work, st);
+    return pairs_gate(c, d_sk, d_lens, n, nb, tb, te, d_cmin, d_sufmin, d_out, cap, d_count, work, st, n_old);
 #if defined(GG_XCHECK)
+  if (n_old) return fail(c, GG_ERR_INVALID_ARG, "gg_pairs_border: the cross-check kernels have no border form");
   if (kern == 2) {
     PairsLaunch a;
     a.sketches = d_sk;
@@ -1108,7 +1126,7 @@ gg_status pairs_core(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, ui
 // the calling thread.
 gg_status pairs_range_to_host(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                               uint64_t tb, uint64_t te, float min_ani, std::vector<gg_pair>& res,
-                              hipStream_t st) {
+                              hipStream_t st, uint32_t n_old) {
   if (n < 2 || tb >= te) return GG_OK;
   uint64_t *d_count, *h_count;
   GG_HIP(c, scratch_t(c, "pair_count", 1, &d_count));
@@ -1120,7 +1138,7 @@ gg_status pairs_range_to_host(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d
     gg_pair* d_out;
     GG_HIP(c, scratch_t(c, "pair_out", cap, &d_out));
     GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-    gg_status ps = pairs_core(c, d_sk, d_lens, n, tb, te, min_ani, d_out, cap, d_count, st);
+    gg_status ps = pairs_core(c, d_sk, d_lens, n, tb, te, min_ani, d_out, cap, d_count, st, n_old);
     if (ps != GG_OK) return ps;
     GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     GG_HIP(c, hipStreamSynchronize(st));

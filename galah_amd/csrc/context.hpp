@@ -229,15 +229,17 @@ gg_status sketch_core(gg_ctx* c, const uint32_t* d_words, uint64_t n_words, cons
                       uint64_t n_runs, uint32_t n_genomes, uint64_t* d_out, uint32_t* d_lens,
                       const uint32_t* d_row_of, hipStream_t st);
 // K2 over tiles [tb, te) of n device sketches; appends to d_out / *d_count.
+// n_old in (0, n): the border instead (gg_pairs_border) -- over every tile,
+// only the pairs (i < j) with j >= n_old; tb and te are not read.
 gg_status pairs_core(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                      uint64_t tb, uint64_t te, float min_ani, gg_pair* d_out, uint64_t cap,
-                     uint64_t* d_count, hipStream_t st);
+                     uint64_t* d_count, hipStream_t st, uint32_t n_old = 0);
 // K2 over tiles [tb, te), passing pairs appended to res, the appended part
 // in (i, j) order.
 constexpr uint64_t kDeviceSortPairs = 4096;  // pairs_range_to_host sorts this many or more on the device
 gg_status pairs_range_to_host(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                               uint64_t tb, uint64_t te, float min_ani, std::vector<gg_pair>& res,
-                              hipStream_t st);
+                              hipStream_t st, uint32_t n_old = 0);
 
 // The finch + finch clustering step over device-resident pairs (cluster.hip):
 // rep_of[] by the rules of cluster_core.hpp.  Synchronises st.

@@ -201,6 +201,7 @@ struct GateLaunch {
   gg_pair* out;
   uint64_t out_cap;
   unsigned long long* count;
+  uint32_t col_min = 0;    // columns below are skipped (gg_pairs_border: the first new row)
 };
 hipError_t launch_gate_build(const GateBuildLaunch& a, hipStream_t st);
 hipError_t launch_pairs_gate(const GateLaunch& a, hipStream_t st);
@@ -414,6 +415,13 @@ struct IndexBuild {
   uint32_t* split_cnt = nullptr;
   uint32_t* split_off = nullptr;
   uint32_t* split_hist = nullptr;  // [256 * 16 * 256]: per super-bin slice, its counts per bucket
+  // Border form (gg_pairs_border): the pairs kernel evaluates rows >= border0
+  // against the rows before them, so an entry of a run in row order names
+  // the members before it (first = the run's start, count = its rank), a
+  // run in arrival order the whole run as ever; runinfo is read only for
+  // those rows, and only their entries add to cost and the longest run.
+  bool border = false;
+  uint32_t border0 = 0;
 };
 struct IndexLaunch {
   const uint64_t* sketches;
@@ -443,6 +451,8 @@ struct IndexLaunch {
   const unsigned long long* cost = nullptr;
   unsigned long long cost_limit = ~0ull;
   bool big_map = false;  // the 2^13-slot partner map (rows that read thousands of members)
+  // border form: rows [row0, n), each against every j < i (tile_begin, tile_end and nb unused)
+  bool border = false;
 };
 // Row offsets, the entry count and the largest hash (info[0], info[1]);
 // then, with the key shift and the sort's bit range, the keys, the sort and

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(kThreads, 8) void pairs_gate_kernel(GateLaunch a) {
   const uint32_t rb = sg.pad;
   const uint32_t row0 = sg.I * GG_PAIR_TILE + rb * p.R;
   if (row0 >= a.n || rb * p.R >= GG_PAIR_TILE) return;
-  const uint32_t c0 = max(sg.J0 * GG_PAIR_TILE, row0 + 1);
+  const uint32_t c0 = max(max(sg.J0 * GG_PAIR_TILE, row0 + 1), a.col_min);
   const uint32_t c1 = min(sg.J1 * GG_PAIR_TILE, a.n);
   if (c0 >= c1) return;
   const uint32_t blk = (sg.I - a.tile_row0) * p.G + rb;

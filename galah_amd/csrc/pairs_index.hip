@@ -27,6 +27,12 @@
 // BASELINE config) the events are a few per entry.  A run longer than
 // kMaxRun (the same hash in thousands of genomes: a highly redundant set)
 // sends the call back to the gate kernel before anything is emitted.
+//
+// Border form (gg_pairs_border: rows >= n_old are new, only pairs with one
+// of them are wanted): step 3 runs for the new rows alone and counts every
+// partner j < i, the build naming for each entry the members before it
+// (IndexBuild::border) and, for a small share of new rows, indexing only the
+// entries whose hash a new row holds (the row-range index).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -701,6 +707,10 @@ __device__ __forceinline__ uint64_t run_reads(uint64_t first, uint32_t count) {
 // A run of equal keys whose members do not all carry the start's low hash
 // word (two hashes with the same top bits: rare) marks its start in the
 // `mixed` bitset; index_mixed_kernel then sorts it and writes its sub-runs.
+// BEFORE (the border form, gg_pairs_border: only rows >= border0 are
+// evaluated, each against the rows before it): an entry of a run in row
+// order names the members before it instead (first = start, count = rank),
+// and only the entries of rows >= border0 add to *cost and the longest run.
 __device__ __forceinline__ uint32_t run_start_back(const uint32_t* __restrict__ keys, uint64_t p, uint32_t key,
                                                    uint32_t max_run) {
   // first position of the run holding p (bounded: a longer run overflows anyway)
@@ -709,12 +719,14 @@ __device__ __forceinline__ uint32_t run_start_back(const uint32_t* __restrict__ 
   return (uint32_t)q;
 }
 
+template <bool BEFORE>
 __global__ __launch_bounds__(256) void index_runs_kernel(const uint32_t* __restrict__ keys,
                                                          const uint64_t* __restrict__ vals, uint64_t total,
                                                          uint32_t stride, uint32_t kbits, uint32_t max_run,
                                                          uint64_t* __restrict__ runinfo, uint32_t* __restrict__ ents,
                                                          uint32_t* __restrict__ mixed, uint32_t* __restrict__ overflow,
-                                                         uint32_t rows_ordered, unsigned long long* __restrict__ cost) {
+                                                         uint32_t rows_ordered, unsigned long long* __restrict__ cost,
+                                                         uint32_t border0) {
   const uint32_t kmask = (1u << kbits) - 1u;
   const uint32_t lane = threadIdx.x & 63;
   unsigned long long reads = 0;
@@ -775,11 +787,20 @@ __global__ __launch_bounds__(256) void index_runs_kernel(const uint32_t* __restr
       atomicOr(overflow, 1u);
       continue;
     }
-    const uint32_t after = end - (uint32_t)p - 1u;  // the run's members after this entry
-    const uint32_t cnt = g < 2 ? 0u : rows_ordered ? after : g;
-    runinfo[(uint64_t)(e >> kbits) * stride + (e & kmask)] = run_reads(rows_ordered ? p + 1 : start, cnt);
-    reads += cnt;
-    gmax = max(gmax, g);
+    if (BEFORE) {
+      const uint32_t cnt = g < 2 ? 0u : rows_ordered ? (uint32_t)p - start : g;  // the members before this entry
+      runinfo[(uint64_t)(e >> kbits) * stride + (e & kmask)] = run_reads(start, cnt);
+      if ((e >> kbits) >= border0) {
+        reads += cnt;
+        gmax = max(gmax, g);
+      }
+    } else {
+      const uint32_t after = end - (uint32_t)p - 1u;  // the run's members after this entry
+      const uint32_t cnt = g < 2 ? 0u : rows_ordered ? after : g;
+      runinfo[(uint64_t)(e >> kbits) * stride + (e & kmask)] = run_reads(rows_ordered ? p + 1 : start, cnt);
+      reads += cnt;
+      gmax = max(gmax, g);
+    }
     if (lo != lo0) atomicOr(&mixed[start >> 5], 1u << (start & 31));
   }
   // (every lane of the wave is here: the sweep's bounds are the wave's)
@@ -791,6 +812,7 @@ __global__ __launch_bounds__(256) void index_runs_kernel(const uint32_t* __restr
 // low word, ents and runinfo rewritten for their members.  One thread per
 // bitset word.
 constexpr uint32_t kMixedRegs = 16;
+template <bool BEFORE>
 __global__ __launch_bounds__(256) void index_mixed_kernel(const uint32_t* __restrict__ keys,
                                                           uint64_t* __restrict__ vals, uint64_t total,
                                                           uint32_t stride, uint32_t kbits,
@@ -842,7 +864,8 @@ __global__ __launch_bounds__(256) void index_mixed_kernel(const uint32_t* __rest
         for (uint64_t q = a; q < b; ++q) {
           const uint32_t v = (uint32_t)vals[q];
           ents[q] = v;
-          runinfo[(uint64_t)(v >> kbits) * stride + (v & kmask)] = run_reads(q + 1, (uint32_t)(b - q - 1));
+          runinfo[(uint64_t)(v >> kbits) * stride + (v & kmask)] =
+              BEFORE ? run_reads(a, (uint32_t)(q - a)) : run_reads(q + 1, (uint32_t)(b - q - 1));
         }
         a = b;
       }
@@ -904,12 +927,12 @@ __global__ __launch_bounds__(256) void bucket_bounds_kernel(const uint16_t* __re
 // its runinfo slot (group start and size g >= 2, or 0) as index_runs_kernel
 // does.  A bucket over kBucketCap entries sets flags[3] (the host rebuilds
 // with the full sort).
-template <int kBucketThreads>
+template <int kBucketThreads, bool BEFORE>
 __global__ __launch_bounds__(kBucketThreads) void index_bucket_kernel(
     const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ nbuckets_p,
     uint64_t total, const uint64_t* __restrict__ sk, uint32_t stride, uint32_t kbits,
     uint32_t max_run, uint64_t* __restrict__ runinfo, uint32_t* __restrict__ ents, uint32_t ents16,
-    uint32_t* __restrict__ flags, unsigned long long* __restrict__ cost) {
+    uint32_t* __restrict__ flags, unsigned long long* __restrict__ cost, uint32_t border0) {
   __shared__ uint64_t tkey[kBucketSlots];
   __shared__ uint32_t tcnt[kBucketSlots + 1];  // group size; after the scan start << 12 | size
   constexpr uint32_t kBucketPer = kBucketCap / kBucketThreads;
@@ -1052,6 +1075,15 @@ __global__ __launch_bounds__(kBucketThreads) void index_bucket_kernel(
         atomicOr(&flags[0], 1u);
         continue;
       }
+      if (BEFORE) {  // (the border form: the members before the entry, costed for the border rows only)
+        const uint32_t cnt = g < 2 ? 0u : sorted_run ? rk : g;
+        runinfo[(uint64_t)(e >> kbits) * stride + (e & kmask)] = run_reads((uint64_t)lo + start, cnt);
+        if ((e >> kbits) >= border0) {
+          reads += cnt;
+          gmax = max(gmax, g);
+        }
+        continue;
+      }
       const uint32_t cnt = g < 2 ? 0u : sorted_run ? g - 1u - rk : g;
       runinfo[(uint64_t)(e >> kbits) * stride + (e & kmask)] =
           run_reads((uint64_t)lo + start + (sorted_run ? rk + 1u : 0u), cnt);
@@ -1087,8 +1119,12 @@ __device__ __forceinline__ uint32_t part_of(uint32_t j, uint32_t plog2) {
 // row's column interval, from the runs of its hashes, then the finch test.
 // Rows whose partners overflow the LDS map are redone in 2, 4, ... passes,
 // each counting one hash class of partners.
+// BORDER (gg_pairs_border): the rows are the new ones, [row0, n), each
+// against every partner j < i -- its runinfo names the members before it,
+// or the whole run (IndexBuild::border) -- and a pair is emitted as (j, i):
+// the expression for total is symmetric in the two rows.
 constexpr uint32_t kMemberLoads = 8;  // run members loaded together per step
-template <bool E16, uint32_t MAPLOG2>
+template <bool E16, uint32_t MAPLOG2, bool BORDER = false>
 __global__ __launch_bounds__(kRowThreads) void index_pairs_kernel(IndexLaunch a) {
   // (MAPLOG2: 11, or 13 for an index whose rows read thousands of run
   // members each -- clusters of thousands of near-identical genomes: their
@@ -1113,7 +1149,8 @@ __global__ __launch_bounds__(kRowThreads) void index_pairs_kernel(IndexLaunch a)
   // run over the limit or a bucket too large left runinfo incomplete)
   if (a.build_flags && ((a.build_flags[0] | a.build_flags[3]) || (a.cost && *a.cost > a.cost_limit))) return;
   uint32_t jlo, jhi;
-  row_columns(i, a.n, a.nb, a.tile_begin, a.tile_end, jlo, jhi);
+  if (BORDER) jlo = 0u, jhi = i;
+  else row_columns(i, a.n, a.nb, a.tile_begin, a.tile_end, jlo, jhi);
   const uint32_t la = a.lens[i];
   if (jlo >= jhi || la == 0) return;
   const uint64_t* ri = a.runinfo + (uint64_t)i * a.stride;
@@ -1198,7 +1235,7 @@ __global__ __launch_bounds__(kRowThreads) void index_pairs_kernel(IndexLaunch a)
       const uint32_t total = xa <= xb ? la + count_le(B, lb, xa) - common : count_le(A, la, xb) + lb - common;
       if (total <= a.tmax && common >= a.cmin[total]) {
         const unsigned long long slot = atomicAdd(a.count, 1ull);
-        if (slot < a.out_cap) a.out[slot] = gg_pair{i, j, common, total};
+        if (slot < a.out_cap) a.out[slot] = BORDER ? gg_pair{j, i, common, total} : gg_pair{i, j, common, total};
       }
     }
     __syncthreads();
@@ -1273,13 +1310,24 @@ hipError_t index_build(const IndexBuild& b, uint64_t total, uint32_t sh, uint32_
   const uint32_t blocks = (uint32_t)(std::min<uint64_t>(8192, std::max<uint64_t>(1, (waves + 4 * kXcds - 1) /
                                                                                   (4 * kXcds))) * kXcds);
   // the entries of shared hashes land in keys_in (free after the sort)
-  hipLaunchKernelGGL(index_runs_kernel, dim3(blocks), dim3(256), 0, st, b.keys_out, b.vals_out, total, b.stride,
-                     b.kbits, b.max_run, b.runinfo, b.keys_in, b.mixed, b.flags, b.bloom ? 0u : 1u, b.cost);
+  const uint32_t rows_ordered = b.bloom ? 0u : 1u;
+  if (b.border)
+    hipLaunchKernelGGL(index_runs_kernel<true>, dim3(blocks), dim3(256), 0, st, b.keys_out, b.vals_out, total,
+                       b.stride, b.kbits, b.max_run, b.runinfo, b.keys_in, b.mixed, b.flags, rows_ordered, b.cost,
+                       b.border0);
+  else
+    hipLaunchKernelGGL(index_runs_kernel<false>, dim3(blocks), dim3(256), 0, st, b.keys_out, b.vals_out, total,
+                       b.stride, b.kbits, b.max_run, b.runinfo, b.keys_in, b.mixed, b.flags, rows_ordered, b.cost, 0u);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const uint64_t words = (total + 31) / 32;
-  hipLaunchKernelGGL(index_mixed_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (words + 255) / 256)), dim3(256), 0,
-                     st, b.keys_out, b.vals_out, total, b.stride, b.kbits, b.mixed, b.runinfo, b.keys_in);
+  const dim3 mixed_grid((uint32_t)std::min<uint64_t>(4096, (words + 255) / 256));
+  if (b.border)
+    hipLaunchKernelGGL(index_mixed_kernel<true>, mixed_grid, dim3(256), 0, st, b.keys_out, b.vals_out, total, b.stride,
+                       b.kbits, b.mixed, b.runinfo, b.keys_in);
+  else
+    hipLaunchKernelGGL(index_mixed_kernel<false>, mixed_grid, dim3(256), 0, st, b.keys_out, b.vals_out, total,
+                       b.stride, b.kbits, b.mixed, b.runinfo, b.keys_in);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(index_cost_sum_kernel, dim3(1), dim3(kCostSlots), 0, st, b.cost);
@@ -1330,11 +1378,15 @@ hipError_t index_build_buckets(const IndexBuild& b, uint64_t total, uint32_t nb_
   auto go = [&](auto kern, int t) {
     hipLaunchKernelGGL(kern, dim3(per_xcd * kXcds), dim3(t), 0, st, vout, b.bstart, nbuckets_d, total, b.sketches,
                        b.stride, b.kbits, b.max_run, b.runinfo, b.keys_in, index_ents16(b.n) ? 1u : 0u, b.flags,
-                       b.cost);
+                       b.cost, b.border ? b.border0 : 0u);
   };
-  if (threads == 256) go(index_bucket_kernel<256>, 256);
-  else if (threads == 512) go(index_bucket_kernel<512>, 512);
-  else go(index_bucket_kernel<1024>, 1024);
+  if (b.border) {
+    if (threads == 256) go(index_bucket_kernel<256, true>, 256);
+    else if (threads == 512) go(index_bucket_kernel<512, true>, 512);
+    else go(index_bucket_kernel<1024, true>, 1024);
+  } else if (threads == 256) go(index_bucket_kernel<256, false>, 256);
+  else if (threads == 512) go(index_bucket_kernel<512, false>, 512);
+  else go(index_bucket_kernel<1024, false>, 1024);
   hipError_t e2 = hipGetLastError();
   if (e2 != hipSuccess) return e2;
   hipLaunchKernelGGL(index_cost_sum_kernel, dim3(1), dim3(kCostSlots), 0, st, b.cost);
@@ -1402,7 +1454,15 @@ hipError_t launch_index_pairs(const IndexLaunch& a, uint32_t n_rows, hipStream_t
   IndexLaunch b = a;
   b.n_rows = n_rows;
   const dim3 grid((n_rows + kXcds - 1) / kXcds * kXcds);
-  if (a.ents16) {
+  if (a.border) {
+    if (a.ents16) {
+      if (a.big_map) hipLaunchKernelGGL((index_pairs_kernel<true, 13, true>), grid, dim3(kRowThreads), 0, st, b);
+      else hipLaunchKernelGGL((index_pairs_kernel<true, 11, true>), grid, dim3(kRowThreads), 0, st, b);
+    } else {
+      if (a.big_map) hipLaunchKernelGGL((index_pairs_kernel<false, 13, true>), grid, dim3(kRowThreads), 0, st, b);
+      else hipLaunchKernelGGL((index_pairs_kernel<false, 11, true>), grid, dim3(kRowThreads), 0, st, b);
+    }
+  } else if (a.ents16) {
     if (a.big_map) hipLaunchKernelGGL((index_pairs_kernel<true, 13>), grid, dim3(kRowThreads), 0, st, b);
     else hipLaunchKernelGGL((index_pairs_kernel<true, 11>), grid, dim3(kRowThreads), 0, st, b);
   } else {

@@ -203,6 +203,45 @@ gg_status gg_pairs_device(gg_ctx* ctx, const uint64_t* d_sketches,
                           float min_ani, gg_pair* d_out, uint64_t out_cap,
                           uint64_t* d_count, void* stream);
 
+/* ---- adding genomes to a finished run: the border -------- */
+/* For rows 0 .. n-1 and n_old <= n, the border is every pair (i < j) with
+ * j >= n_old that passes gg_pairs' test, so that
+ *   gg_pairs(rows[0:n]) == gg_pairs(rows[0:n_old]) U gg_pairs_border(rows[0:n], n_old),
+ * the two sets disjoint.  The sketch matrix stays as it is: the old rows
+ * first, the new rows after them, in the caller's order; K2 evaluates only
+ * the new rows, each against every row before it.  n_old == 0 gives
+ * gg_pairs, n_old == n nothing, n_old > n GG_ERR_INVALID_ARG.  A multi-device
+ * context acts on its first member (the border is not sharded).
+ * gg_pair_paths and gg_fallbacks count a border call like any other. */
+
+/* Host buffers in and out, as gg_pairs: *out library-owned (gg_free), sorted
+ * by (i, j); lens[g] <= sketch_size is checked. */
+gg_status gg_pairs_border(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                          uint32_t n_old, float min_ani, gg_pair** out, uint64_t* n_out);
+/* Device-resident, the contract of gg_pairs_device (appends unsorted to d_out,
+ * *d_count incremented by the number found, entries past out_cap dropped,
+ * asynchronous on `stream`).  A caller that keeps the matrix resident
+ * between updates -- a torch tensor of [capacity x sketch_size] u64 with
+ * spare rows, say -- writes each batch of new sketches after the rows it
+ * holds and calls this with the grown n: nothing is moved or uploaded again. */
+gg_status gg_pairs_border_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                 uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t out_cap,
+                                 uint64_t* d_count, void* stream);
+/* On the host (n_new * n merges at most); no device, no ctx. */
+gg_status gg_pairs_border_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
+                               uint32_t sketch_size, int kmer_length, float min_ani,
+                               gg_pair** out, uint64_t* n_out);
+/* A finished run carried forward by files: only new_paths are read and
+ * sketched (cache_dir as gg_sketch_files, NULL: none) into new_hashes
+ * [n_new x sketch_size] and new_lens [n_new]; they are placed after the old
+ * rows (old_sketches [n_old x sketch_size], old_lens, as the earlier run
+ * returned them) on the device, and the border comes back sorted by (i, j)
+ * with its f32 ANI (gg_free both); indices are into old + new. */
+gg_status gg_update_files(gg_ctx* ctx, const uint64_t* old_sketches, const uint32_t* old_lens, uint32_t n_old,
+                          const char* const* new_paths, uint32_t n_new, float min_ani, const char* cache_dir,
+                          uint64_t* new_hashes, uint32_t* new_lens,
+                          gg_pair** pairs, float** ani, uint64_t* n_out);
+
 /* ---- the fused FinchPreclusterer::distances body ------------------------ */
 /* paths -> sorted passing pairs plus their f32 ANI (src/finch.rs:70 value).
  * Files are streamed: read, gunzipped and packed on the host threads

@@ -202,6 +202,20 @@ extern "C" {
                            tile_end: u64, min_ani: f32, d_out: *mut gg_pair, out_cap: u64, d_count: *mut u64,
                            stream: *mut c_void) -> GgStatus;
 
+    // adding genomes to a finished run: the pairs (i < j) with j >= n_old
+    pub fn gg_pairs_border(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, n_old: u32, min_ani: f32,
+                           out: *mut *mut gg_pair, n_out: *mut u64) -> GgStatus;
+    pub fn gg_pairs_border_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32, n_old: u32,
+                                  min_ani: f32, d_out: *mut gg_pair, out_cap: u64, d_count: *mut u64,
+                                  stream: *mut c_void) -> GgStatus;
+    pub fn gg_pairs_border_host(sketches: *const u64, lens: *const u32, n: u32, n_old: u32, sketch_size: u32,
+                                kmer_length: c_int, min_ani: f32, out: *mut *mut gg_pair, n_out: *mut u64)
+                                -> GgStatus;
+    pub fn gg_update_files(ctx: *mut gg_ctx, old_sketches: *const u64, old_lens: *const u32, n_old: u32,
+                           new_paths: *const *const c_char, n_new: u32, min_ani: f32, cache_dir: *const c_char,
+                           new_hashes: *mut u64, new_lens: *mut u32, pairs: *mut *mut gg_pair, ani: *mut *mut f32,
+                           n_out: *mut u64) -> GgStatus;
+
     // the fused FinchPreclusterer::distances body
     pub fn gg_precluster_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
                                pairs: *mut *mut gg_pair, ani: *mut *mut f32, n_out: *mut u64) -> GgStatus;
