@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "gg_ani_pairs_host", "gg_ani_pairs", "gg_ani_pairs_device",
     "gg_validate_clusters_host", "gg_validate_clusters", "gg_validate_files",
     "gg_pairs_border", "gg_pairs_border_device", "gg_pairs_border_host", "gg_update_files",
+    "gg_preclusters", "gg_preclusters_device",
 )
 
 GG_OK = 0
@@ -180,6 +181,8 @@ _sig("gg_synth_mixed_device", _i32, [_vp, _u32, _u32, _vp, _u32, ctypes.c_float,
                                      _u64, ctypes.POINTER(_u64), _vp])
 _sig("gg_partition_preclusters", _i32, [_u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32)])
 _sig("gg_precluster_pairs", _i32, [_u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp])
+_sig("gg_preclusters", _i32, [_vp, _u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32), _vp, _vp])
+_sig("gg_preclusters_device", _i32, [_vp, _u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32), _vp, _vp, _vp])
 _sig("gg_cluster_pairs_host", _i32, [_u32, _vp, _vp, _u64, ctypes.c_float, _vp])
 _sig("gg_cluster_pairs", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float, _vp])
 _sig("gg_cluster_pairs_device", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float, _vp, _vp])
@@ -220,6 +223,7 @@ KERNEL_SKETCH, KERNEL_FINALIZE, KERNEL_PAIRS, KERNEL_PAIRS_INDEX = 0, 1, 2, 3
  KERNEL_PARSE, KERNEL_UPLOAD) = range(4, 11)
 KERNEL_CLUSTER = 11  # every kernel of cluster_pairs / cluster_pairs_device (work: pairs)
 KERNEL_ANI_PAIRS = 12  # the named-pair kernel of ani_pairs / ani_pairs_device / validate_clusters (work: listed pairs)
+KERNEL_PRECLUSTER = 13  # every kernel of preclusters / preclusters_device (work: pairs)
 INGEST_KERNELS = {"search": KERNEL_INFLATE_SEARCH, "decode": KERNEL_INFLATE_DECODE, "expand": KERNEL_INFLATE_EXPAND,
                   "resolve": KERNEL_INFLATE_RESOLVE, "crc": KERNEL_INFLATE_CRC, "parse": KERNEL_PARSE,
                   "upload": KERNEL_UPLOAD}
@@ -1002,6 +1006,26 @@ class Context:
             raise self._err(st)
         return rep_of[:n_genomes]
 
+    def preclusters(self, n_genomes, pairs, with_pairs=True):
+        """partition_preclusters + precluster_pairs as one call on the
+        context's (first) device -> (members, offsets, local, pair_offsets),
+        the same arrays as the two host functions give (duplicates of one pair
+        in ascending src); local and pair_offsets are None without with_pairs."""
+        p = _as_pairs(pairs)
+        members = np.zeros(max(n_genomes, 1), np.uint32)
+        offsets = np.zeros(n_genomes + 1, np.uint32)
+        local = np.zeros(max(len(p), 1), LOCAL_PAIR_DTYPE) if with_pairs else None
+        poff = np.zeros(n_genomes + 1, np.uint64) if with_pairs else None
+        ns = _u32()
+        st = _L.gg_preclusters(self._c, n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), ctypes.byref(ns),
+                               _ptr(local) if with_pairs else None, _ptr(poff) if with_pairs else None)
+        if st != GG_OK:
+            raise self._err(st)
+        members, offsets = members[:n_genomes], offsets[:ns.value + 1].copy()
+        if not with_pairs:
+            return members, offsets, None, None
+        return members, offsets, local[:len(p)], poff[:ns.value + 1].copy()
+
     def ani_pairs(self, sketches, lens, pairs):
         """ani_pairs_host on the context's (first) device, one kernel launch
         for the whole list -> (PAIR_DTYPE array in the order given, ani f32)."""
@@ -1129,6 +1153,25 @@ class Context:
                                         None if stream is None else stream)
         if st != GG_OK:
             raise self._err(st)
+
+    def preclusters_device(self, n_genomes, d_pairs, n_pairs, d_members, d_offsets, d_local=None,
+                           d_pair_offsets=None, stream=None):
+        """preclusters over device-resident tensors (or pointers): d_pairs
+        n_pairs 16-byte gg_pair records, d_members u32 [n_genomes], d_offsets
+        u32 [n_genomes + 1], d_local n_pairs 16-byte gg_local_pair records,
+        d_pair_offsets u64 [n_genomes + 1] (both None: the partition only)
+        -> n_sets.  Synchronises the stream; the input is not checked: a pair
+        with an index >= n_genomes is left out, and d_pair_offsets[n_sets] is
+        the number of local pairs written."""
+        ns = _u32()
+        st = _L.gg_preclusters_device(self._c, n_genomes, _dev_ptr(d_pairs), n_pairs, _dev_ptr(d_members),
+                                      _dev_ptr(d_offsets), ctypes.byref(ns),
+                                      None if d_local is None else _dev_ptr(d_local),
+                                      None if d_pair_offsets is None else _dev_ptr(d_pair_offsets),
+                                      None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+        return ns.value
 
     def ani_pairs_device(self, d_sketches, d_lens, n, d_list, m, stream=None):
         """ani_pairs over device-resident tensors: d_sketches [n, s] u64,

@@ -1575,6 +1575,11 @@ gg_status gg_info_line(const gg_ctx* ctx, char* buf, size_t cap) {
     snprintf(line, sizeof line, "; cluster round launches %llu", (unsigned long long)first->cluster_rounds);
     out += line;
   }
+  // the last gg_preclusters(_device) call (on the first member): its pointer-jumping launches
+  if (first->precluster_calls) {
+    snprintf(line, sizeof line, "; precluster jump launches %llu", (unsigned long long)first->precluster_jumps);
+    out += line;
+  }
   // device / pinned scratch buffers grown since the context was created
   // (and the wall time that took: hipFree waits for the device), its lanes'
   // included -- a call that grows one runs long

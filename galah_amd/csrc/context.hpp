@@ -156,6 +156,9 @@ struct gg_ctx {
   // gg_cluster_pairs(_device) calls on this device, and the launches of the
   // representative-round kernel in the last one (gg_info_line)
   uint64_t cluster_calls = 0, cluster_rounds = 0;
+  // gg_preclusters(_device) calls on this device, and the pointer-jumping
+  // launches of the last one (gg_info_line)
+  uint64_t precluster_calls = 0, precluster_jumps = 0;
   // scratch / host-scratch buffers regrown (and the wall ms it took), gg_info_line
   uint64_t scratch_regrows = 0;
   double scratch_regrow_ms = 0;
@@ -245,6 +248,11 @@ gg_status pairs_range_to_host(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d
 // rep_of[] by the rules of cluster_core.hpp.  Synchronises st.
 gg_status cluster_device(gg_ctx* c, uint32_t n, const gg_pair* d_pairs, const float* d_ani, uint64_t n_pairs, float T,
                          uint32_t* d_rep_of, hipStream_t st);
+// The precluster step over device-resident pairs (precluster.hip): members,
+// offsets and, with d_pair_offsets, the local pairs.  Synchronises st.
+gg_status preclusters_device(gg_ctx* c, uint32_t n, const gg_pair* d_pairs, uint64_t n_pairs, uint32_t* d_members,
+                             uint32_t* d_offsets, uint32_t* n_sets, gg_local_pair* d_local, uint64_t* d_pair_offsets,
+                             hipStream_t st);
 // The input checks of its host-input forms (cluster.cpp; the thread's error is set).
 gg_status cluster_check_input(const char* who, uint32_t n_genomes, const gg_pair* pairs, const float* ani,
                               uint64_t n_pairs, float cluster_ani, const uint32_t* rep_of);

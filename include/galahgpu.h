@@ -385,6 +385,29 @@ gg_status gg_precluster_pairs(uint32_t n_genomes, const gg_pair* pairs,
                               const uint32_t* offsets, uint32_t n_sets,
                               gg_local_pair* out, uint64_t* pair_offsets);
 
+/* The two calls above as one, on the context's (first) device (DESIGN.md
+ * 4.8): connected components by lock-free hooking and pointer jumping, the
+ * sets and the local pairs ordered by radix sorts.  Host arrays in and out,
+ * the output contract of the two host calls: members [n_genomes], offsets
+ * [n_genomes + 1], *n_sets; local [n_pairs] grouped by precluster and sorted
+ * by (i, j) inside it, src = index into pairs, duplicates of one pair in
+ * ascending src; pair_offsets [n_genomes + 1] of which n_sets + 1 are
+ * written.  local and pair_offsets may both be NULL: the partition only.
+ * Pairs in any order and either orientation, duplicates allowed, i == j
+ * allowed (the local pair (a, a)).  GG_ERR_INVALID_ARG for an index >=
+ * n_genomes, for n_pairs or n_genomes >= 2^31 and for null arguments. */
+gg_status gg_preclusters(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* pairs, uint64_t n_pairs,
+                         uint32_t* members, uint32_t* offsets, uint32_t* n_sets,
+                         gg_local_pair* local, uint64_t* pair_offsets);
+/* Device-resident in and out on `stream`; *n_sets is a host word.
+ * Synchronises the stream internally (the pointer-jumping launches go on
+ * until a word read back says none of them wrote).  The input is not
+ * checked: a pair with an index >= n_genomes is never followed and is left
+ * out of d_local, and d_pair_offsets[n_sets] is the number of pairs written. */
+gg_status gg_preclusters_device(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* d_pairs, uint64_t n_pairs,
+                                uint32_t* d_members, uint32_t* d_offsets, uint32_t* n_sets,
+                                gg_local_pair* d_local, uint64_t* d_pair_offsets, void* stream);
+
 /* ---- finch + finch clustering ---------------------------- */
 /* src/clusterer.rs:14-125 when the preclusterer and the clusterer are both
  * finch (skip_clusterer, :29-33, :180-185): the result is a function of the
@@ -529,11 +552,13 @@ void gg_free(void* p);
  * and the PCIe upload of each staged batch (bytes).  GG_KERNEL_CLUSTER is
  * every kernel of gg_cluster_pairs(_device) (work: pairs, counted on the
  * first).  GG_KERNEL_ANI_PAIRS is the named-pair kernel of gg_ani_pairs(_device)
- * and gg_validate_clusters (work: listed pairs). */
+ * and gg_validate_clusters (work: listed pairs).  GG_KERNEL_PRECLUSTER is
+ * every kernel of gg_preclusters(_device) (work: pairs, counted on the
+ * first). */
 enum { GG_KERNEL_SKETCH = 0, GG_KERNEL_FINALIZE = 1, GG_KERNEL_PAIRS = 2, GG_KERNEL_PAIRS_INDEX = 3,
        GG_KERNEL_INFLATE_SEARCH = 4, GG_KERNEL_INFLATE_DECODE = 5, GG_KERNEL_INFLATE_EXPAND = 6,
        GG_KERNEL_INFLATE_RESOLVE = 7, GG_KERNEL_INFLATE_CRC = 8, GG_KERNEL_PARSE = 9, GG_KERNEL_UPLOAD = 10,
-       GG_KERNEL_CLUSTER = 11, GG_KERNEL_ANI_PAIRS = 12, GG_KERNEL_COUNT = 13 };
+       GG_KERNEL_CLUSTER = 11, GG_KERNEL_ANI_PAIRS = 12, GG_KERNEL_PRECLUSTER = 13, GG_KERNEL_COUNT = 14 };
 typedef struct gg_kernel_stats {
   double ms;
   uint64_t launches;

@@ -51,7 +51,8 @@ pub const GG_KERNEL_PARSE: c_int = 9;
 pub const GG_KERNEL_UPLOAD: c_int = 10;
 pub const GG_KERNEL_CLUSTER: c_int = 11;
 pub const GG_KERNEL_ANI_PAIRS: c_int = 12;
-pub const GG_KERNEL_COUNT: c_int = 13;
+pub const GG_KERNEL_PRECLUSTER: c_int = 13;
+pub const GG_KERNEL_COUNT: c_int = 14;
 
 pub const GG_PATH_INDEX: c_int = 0;
 pub const GG_PATH_INDEX_ABANDONED: c_int = 1;
@@ -250,6 +251,14 @@ extern "C" {
                                     offsets: *mut u32, n_sets: *mut u32) -> GgStatus;
     pub fn gg_precluster_pairs(n_genomes: u32, pairs: *const gg_pair, n_pairs: u64, members: *const u32,
                                offsets: *const u32, n_sets: u32, out: *mut gg_local_pair, pair_offsets: *mut u64)
+        -> GgStatus;
+    // the two calls above as one, on the context's first device
+    pub fn gg_preclusters(ctx: *mut gg_ctx, n_genomes: u32, pairs: *const gg_pair, n_pairs: u64, members: *mut u32,
+                          offsets: *mut u32, n_sets: *mut u32, local: *mut gg_local_pair, pair_offsets: *mut u64)
+        -> GgStatus;
+    pub fn gg_preclusters_device(ctx: *mut gg_ctx, n_genomes: u32, d_pairs: *const gg_pair, n_pairs: u64,
+                                 d_members: *mut u32, d_offsets: *mut u32, n_sets: *mut u32,
+                                 d_local: *mut gg_local_pair, d_pair_offsets: *mut u64, stream: *mut c_void)
         -> GgStatus;
 
     // finch + finch clustering (src/clusterer.rs:155-225, :316-406 with skip_clusterer)
