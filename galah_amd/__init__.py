@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "gg_validate_clusters_host", "gg_validate_clusters", "gg_validate_files",
     "gg_pairs_border", "gg_pairs_border_device", "gg_pairs_border_host", "gg_update_files",
     "gg_preclusters", "gg_preclusters_device",
+    "gg_ani_f32_device", "gg_cluster_rows_device", "gg_cluster_files_resident",
 )
 
 GG_OK = 0
@@ -189,6 +190,22 @@ _sig("gg_cluster_pairs_device", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float
 _sig("gg_clusters_from_reps", _i32, [_u32, _vp, _vp, _vp, ctypes.POINTER(_u32)])
 _sig("gg_cluster_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_float,
                                 ctypes.c_char_p, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+
+
+class _ClusterSummary(ctypes.Structure):
+    _fields_ = [("n_pairs", ctypes.c_uint64), ("ani_rechecked", ctypes.c_uint64), ("n_preclusters", ctypes.c_uint32),
+                ("largest_precluster", ctypes.c_uint32), ("pair_passes", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
+
+
+_sig("gg_ani_f32_device", _i32, [_vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_u64), _vp])
+_sig("gg_cluster_rows_device", _i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.c_float, _vp,
+                                      ctypes.POINTER(_ClusterSummary), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp])
+_sig("gg_cluster_files_resident", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_char_p, _vp, ctypes.POINTER(_ClusterSummary)])
 _sig("gg_ani_pairs_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _u64, _vp])
 _sig("gg_ani_pairs", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
 _sig("gg_ani_pairs_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
@@ -1084,6 +1101,23 @@ class Context:
         pairs, ani = self._pairs_ani(pp, ap, cnt.value)
         return rep_of[:n], pairs, ani
 
+    def cluster_files_resident(self, paths, min_ani, cluster_ani, cache_dir=None):
+        """cluster_files(..., want_pairs=False) with the pair list staying in
+        device memory (gg_cluster_files_resident) -> (rep_of, summary): summary
+        a dict of n_pairs, ani_rechecked, n_preclusters, largest_precluster and
+        pair_passes.  A multi-device context takes cluster_files' path and
+        reports ani_rechecked and pair_passes as 0; the rest is the same."""
+        n = len(paths)
+        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        rep_of = np.zeros(max(n, 1), np.uint32)
+        summary = _ClusterSummary()
+        st = _L.gg_cluster_files_resident(self._c, arr, n, ctypes.c_float(min_ani), ctypes.c_float(cluster_ani),
+                                          None if cache_dir is None else os.fsencode(cache_dir), _ptr(rep_of),
+                                          ctypes.byref(summary))
+        if st != GG_OK:
+            raise self._err(st)
+        return rep_of[:n], summary.as_dict()
+
     def precluster_files_each(self, paths, min_ani, each, cache_dir=None):
         """precluster_files, and every compared pair (i < j, all N (N - 1) / 2,
         whatever the ANI) handed to each(block) in (i, j) order as PAIR_DTYPE
@@ -1153,6 +1187,42 @@ class Context:
                                         None if stream is None else stream)
         if st != GG_OK:
             raise self._err(st)
+
+    def ani_f32_device(self, d_pairs, n_pairs, d_ani, d_ani_f64=None, stream=None):
+        """d_ani[p] = ani_f32(common, total, k) of the n_pairs 16-byte gg_pair
+        records at d_pairs, bit for bit, computed on the device; d_ani_f64
+        (optional) the f64 before rounding -> the number of entries the host
+        recomputed.  Synchronises the stream."""
+        cnt = _u64()
+        st = _L.gg_ani_f32_device(self._c, _dev_ptr(d_pairs), n_pairs, _dev_ptr(d_ani),
+                                  None if d_ani_f64 is None else _dev_ptr(d_ani_f64), ctypes.byref(cnt),
+                                  None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+        return cnt.value
+
+    def cluster_rows_device(self, d_sketches, d_lens, n, min_ani, cluster_ani, d_rep_of, want_summary=True,
+                            stream=None):
+        """pairs + ani_f32 + cluster_pairs over device-resident rows, the pair
+        list never leaving device memory: d_sketches [n, s] u64, d_lens [n]
+        u32, d_rep_of u32 [n] (every entry is written) -> (summary, d_pairs,
+        d_ani, n_pairs): summary as cluster_files_resident gives it (None
+        without want_summary), d_pairs and d_ani the device addresses (ints) of
+        the context's n_pairs unsorted gg_pair records and their f32 ANI, valid
+        until the next call on the context.  Without want_summary the
+        partition into preclusters is not computed and n_pairs is None.
+        Synchronises the stream."""
+        summary = _ClusterSummary()
+        pp, ap = _vp(), _vp()
+        st = _L.gg_cluster_rows_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, ctypes.c_float(min_ani),
+                                       ctypes.c_float(cluster_ani), _dev_ptr(d_rep_of),
+                                       ctypes.byref(summary) if want_summary else None,
+                                       ctypes.byref(pp), ctypes.byref(ap), None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+        if not want_summary:
+            return None, pp.value or 0, ap.value or 0, None
+        return summary.as_dict(), pp.value or 0, ap.value or 0, int(summary.n_pairs)
 
     def preclusters_device(self, n_genomes, d_pairs, n_pairs, d_members, d_offsets, d_local=None,
                            d_pair_offsets=None, stream=None):
@@ -1588,7 +1658,8 @@ def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
     each with its representative first.  Built for the case the reference
     marks skip_clusterer (:29-33): preclusterer and clusterer both "finch",
     the result then being a function of the pair cache, computed on the GPU
-    (gg_cluster_files).  Any other combination raises: the external-clusterer
+    (gg_cluster_files_resident on one device, the pairs never leaving it;
+    gg_cluster_files on several).  Any other combination raises: the external-clusterer
     flow is not part of this library."""
     log = logging.getLogger("galah")
     clusterer.initialise()
@@ -1603,17 +1674,24 @@ def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
     try:
         ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
         log.info("Sketching MinHash representations of each genome with finch ..")  # src/finch.rs:46
-        rep_of, pairs, _ = ctx.cluster_files(paths, float(np.float32(preclusterer.min_ani)),
-                                             float(np.float32(clusterer.get_ani_threshold())), cache_dir=cache_dir)
+        min_ani, T = float(np.float32(preclusterer.min_ani)), float(np.float32(clusterer.get_ani_threshold()))
+        if ctx.device_count == 1:
+            # one device: the pair list stays in its memory, the preclusters'
+            # count and largest size come back with rep_of
+            rep_of, summary = ctx.cluster_files_resident(paths, min_ani, T, cache_dir=cache_dir)
+            n_sets, largest = summary["n_preclusters"], summary["largest_precluster"]
+        else:
+            rep_of, pairs, _ = ctx.cluster_files(paths, min_ani, T, cache_dir=cache_dir)
+            if paths:
+                _, offsets = partition_preclusters(len(paths), pairs)
+                n_sets, largest = len(offsets) - 1, int(offsets[1] - offsets[0])
     except GalahGpuError as e:
         raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
     log.info("Finished sketching genomes")  # src/finch.rs:48
     log.info(ctx.info_line())
     log.info("Preclustering ..")  # :38
     if paths:
-        _, offsets = partition_preclusters(len(paths), pairs)
-        log.info("Found %d preclusters. The largest contained %d genomes", len(offsets) - 1,
-                 int(offsets[1] - offsets[0]))  # :59-63
+        log.info("Found %d preclusters. The largest contained %d genomes", n_sets, largest)  # :59-63
     log.info("Finding representative genomes and assigning all genomes to these ..")  # :65
     return clusters_from_reps(rep_of)
 

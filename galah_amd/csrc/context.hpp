@@ -253,6 +253,19 @@ gg_status cluster_device(gg_ctx* c, uint32_t n, const gg_pair* d_pairs, const fl
 gg_status preclusters_device(gg_ctx* c, uint32_t n, const gg_pair* d_pairs, uint64_t n_pairs, uint32_t* d_members,
                              uint32_t* d_offsets, uint32_t* n_sets, gg_local_pair* d_local, uint64_t* d_pair_offsets,
                              hipStream_t st);
+// The f32 ANI of device-resident pairs (ani_f32.hip, by ani_core.hpp): d_ani[p]
+// = gg_ani_f32 of pair p bit for bit, d_ani_f64 (may be null) the f64 before
+// rounding, *n_rechecked (may be null) the entries the host recomputed.
+// Synchronises st.
+gg_status ani_f32_device(gg_ctx* c, const gg_pair* d_pairs, uint64_t n_pairs, float* d_ani, double* d_ani_f64,
+                         uint64_t* n_rechecked, hipStream_t st);
+// Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
+// ani_f32_device, cluster_device; with sum, the partition of
+// preclusters_device.  *d_pairs / *d_ani (may be null) receive the scratch
+// arrays.  Synchronises st.
+gg_status cluster_rows_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, float min_ani,
+                              float T, uint32_t* d_rep_of, gg_cluster_summary* sum, const gg_pair** d_pairs,
+                              const float** d_ani, hipStream_t st);
 // The input checks of its host-input forms (cluster.cpp; the thread's error is set).
 gg_status cluster_check_input(const char* who, uint32_t n_genomes, const gg_pair* pairs, const float* ani,
                               uint64_t n_pairs, float cluster_ani, const uint32_t* rep_of);

@@ -1115,6 +1115,64 @@ gg_status gg_precluster_files(gg_ctx* ctx, const char* const* paths, uint32_t n_
   return gg_precluster_files_cached(ctx, paths, n_paths, min_ani, nullptr, pairs, ani, n_out, nullptr);
 }
 
+gg_status gg_cluster_files_resident(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                    float cluster_ani, const char* cache_dir, uint32_t* rep_of,
+                                    gg_cluster_summary* summary) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  if (summary) *summary = gg_cluster_summary{};
+  if (n_paths && (!paths || !rep_of)) return fail(ctx, GG_ERR_INVALID_ARG, "gg_cluster_files_resident: null argument");
+  if (std::isnan(min_ani) || std::isnan(cluster_ani))
+    return fail(ctx, GG_ERR_INVALID_ARG, "gg_cluster_files_resident: min_ani or cluster_ani is NaN");
+  const std::vector<gg_ctx*> ms = members(ctx);
+  if (ms.size() > 1) {
+    // the resident call is not sharded: gg_cluster_files' path, the summary
+    // from the host partition of its pairs
+    gg_pair* p = nullptr;
+    float* a = nullptr;
+    uint64_t n = 0;
+    gg_status st = gg_cluster_files(ctx, paths, n_paths, min_ani, cluster_ani, cache_dir, rep_of, &p, &a, &n);
+    if (st == GG_OK && summary && n_paths) {
+      std::vector<uint32_t> mem(n_paths), off((size_t)n_paths + 1);
+      uint32_t n_sets = 0;
+      st = gg_partition_preclusters(n_paths, p, n, mem.data(), off.data(), &n_sets);
+      if (st == GG_OK) {
+        summary->n_pairs = n;
+        summary->n_preclusters = n_sets;
+        summary->largest_precluster = off[1] - off[0];
+      } else {
+        fail(ctx, st, gg_thread_last_error());
+      }
+    }
+    gg_free(p);
+    gg_free(a);
+    return st;
+  }
+  for (double& x : ctx->phase_ms) x = 0.0;
+  std::vector<Rows> rows;
+  std::vector<RowSpan> spans;
+  auto t0 = Clock::now();
+  // (every file is read and sketched, even a lone one: gg_precluster_files_cached)
+  gg_status st = sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, nullptr, nullptr, nullptr);
+  if (st != GG_OK) return st;
+  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
+  if (n_paths == 0) return GG_OK;
+  t0 = Clock::now();
+  gg_ctx* m = ms[0];
+  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+  uint32_t* d_rep = nullptr;
+  GG_HIP(m, scratch_t(m, "rs_rep", (size_t)n_paths, &d_rep));
+  st = cluster_rows_device(m, rows[0].sk, rows[0].len, n_paths, min_ani, cluster_ani, d_rep, summary, nullptr, nullptr,
+                           m->stream);
+  if (st != GG_OK) {
+    if (summary) *summary = gg_cluster_summary{};
+    return st;
+  }
+  GG_HIP(m, hipMemcpyAsync(rep_of, d_rep, (size_t)n_paths * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
+  return GG_OK;
+}
+
 gg_status gg_precluster_files_each(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
                                    const char* cache_dir, gg_pair_sink sink, void* user, gg_pair** pairs,
                                    float** ani, uint64_t* n_out, uint32_t* n_cached) {

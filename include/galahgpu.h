@@ -456,6 +456,53 @@ gg_status gg_cluster_files(gg_ctx* ctx, const char* const* paths, uint32_t n_pat
                            float cluster_ani, const char* cache_dir, uint32_t* rep_of,
                            gg_pair** pairs, float** ani, uint64_t* n_out);
 
+/* ---- clustering from resident sketches ------------------- */
+/* The chain of the device forms above with the pair list staying in device
+ * memory: K2, the f32 ANI of every pair computed on the device, the
+ * clustering step.  The pairs are not sorted on the way: neither the
+ * clustering rules nor the partition into preclusters depend on their order
+ * (DESIGN.md 4.5, 4.8).  Results equal those of the host-array entry points. */
+
+/* d_ani[p] = gg_ani_f32(d_pairs[p].common, d_pairs[p].total, k of the context), bit for bit;
+ * d_ani_f64 (may be NULL) the f64 before rounding; *n_rechecked (may be NULL) the entries the
+ * host recomputed (those whose f32 the device's log could have rounded
+ * otherwise: galah_amd/csrc/ani_core.hpp).  d_pairs 16-byte aligned,
+ * n_pairs < 2^31.  Synchronises the stream. */
+gg_status gg_ani_f32_device(gg_ctx* ctx, const gg_pair* d_pairs, uint64_t n_pairs, float* d_ani,
+                            double* d_ani_f64, uint64_t* n_rechecked, void* stream);
+
+typedef struct gg_cluster_summary {
+  uint64_t n_pairs;            /* pairs >= min_ani */
+  uint64_t ani_rechecked;      /* of them, f32 values the host recomputed (gg_ani_f32_device) */
+  uint32_t n_preclusters;      /* connected components, singletons included */
+  uint32_t largest_precluster;
+  uint32_t pair_passes;        /* 1, or 2 after the capacity retry (0: fewer than 2 genomes) */
+  uint32_t reserved;
+} gg_cluster_summary;
+
+/* rows resident -> rep_of resident; what gg_pairs + gg_ani_f32 + gg_cluster_pairs give, on
+ * the context's (first) device.  d_sketches / d_lens as gg_pairs_device takes
+ * them, d_rep_of [n] (every entry is written; n < 2: every genome its own
+ * representative).  *d_pairs / *d_ani (may be NULL) receive context-owned device arrays of
+ * summary->n_pairs entries, unsorted, valid until the next call on the context.  summary may
+ * be NULL (the partition into preclusters is then not computed).
+ * GG_ERR_INVALID_ARG for a NaN threshold, null buffers, n >= 2^31, or 2^31
+ * passing pairs or more.  Synchronises the stream. */
+gg_status gg_cluster_rows_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                 float min_ani, float cluster_ani, uint32_t* d_rep_of,
+                                 gg_cluster_summary* summary, const gg_pair** d_pairs, const float** d_ani,
+                                 void* stream);
+
+/* gg_cluster_files without the pair list on the host: the files sketched as
+ * gg_precluster_files_cached does, then gg_cluster_rows_device over the rows
+ * and rep_of [n_paths] copied back.  A multi-device context takes
+ * gg_cluster_files' path instead (the resident call is not sharded) and
+ * fills summary from the host partition, ani_rechecked and pair_passes 0:
+ * rep_of and the other fields are the same either way.  summary may be NULL. */
+gg_status gg_cluster_files_resident(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                    float cluster_ani, const char* cache_dir, uint32_t* rep_of,
+                                    gg_cluster_summary* summary);
+
 /* ---- ANI of named pairs, cluster validation -------------- */
 /* src/lib.rs:29-37 ClusterDistanceFinder::calculate_ani(fasta1, fasta2) for
  * a whole list at once: list[p].i and list[p].j name two rows of the sketch

@@ -158,6 +158,19 @@ pub struct gg_validation {
     pub rep_bad: u64,
 }
 
+/// What `gg_cluster_rows_device` / `gg_cluster_files_resident` report beside
+/// `rep_of` (`gg_cluster_summary`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gg_cluster_summary {
+    pub n_pairs: u64,
+    pub ani_rechecked: u64,
+    pub n_preclusters: u32,
+    pub largest_precluster: u32,
+    pub pair_passes: u32,
+    pub reserved: u32,
+}
+
 /// `gg_pair_sink`: a block of compared pairs; return 0 to go on.
 pub type gg_pair_sink = Option<unsafe extern "C" fn(user: *mut c_void, pairs: *const gg_pair, n: u64) -> c_int>;
 
@@ -274,6 +287,17 @@ extern "C" {
     pub fn gg_cluster_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
                             cluster_ani: f32, cache_dir: *const c_char, rep_of: *mut u32, pairs: *mut *mut gg_pair,
                             ani: *mut *mut f32, n_out: *mut u64) -> GgStatus;
+
+    // clustering from resident sketches: the f32 ANI on the device, the pair list stays there
+    pub fn gg_ani_f32_device(ctx: *mut gg_ctx, d_pairs: *const gg_pair, n_pairs: u64, d_ani: *mut f32,
+                             d_ani_f64: *mut f64, n_rechecked: *mut u64, stream: *mut c_void) -> GgStatus;
+    pub fn gg_cluster_rows_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32, min_ani: f32,
+                                  cluster_ani: f32, d_rep_of: *mut u32, summary: *mut gg_cluster_summary,
+                                  d_pairs: *mut *const gg_pair, d_ani: *mut *const f32, stream: *mut c_void)
+        -> GgStatus;
+    pub fn gg_cluster_files_resident(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
+                                     cluster_ani: f32, cache_dir: *const c_char, rep_of: *mut u32,
+                                     summary: *mut gg_cluster_summary) -> GgStatus;
 
     // ANI of named pairs (src/lib.rs:29-37), cluster validation (src/cluster_validation.rs:7-78)
     pub fn gg_ani_pairs_host(sketches: *const u64, lens: *const u32, n: u32, sketch_size: u32, kmer_length: c_int,
