@@ -25,9 +25,12 @@
 //   * Bottom-s selection is a threshold prefilter: a k-mer survives iff
 //     h <= tau[g] where tau[g] ~ C*s/nk_g * 2^64, so only ~C*s of the
 //     ~nk_g hashes per genome reach a per-genome open-addressing set in HBM
-//     (atomicCAS, duplicates collapse).  The test runs on the high words of
-//     the two finalisers first; the k-mers that pass go to a per-wave LDS
-//     queue whose drain finishes the exact hash and inserts.  The finalize
+//     (atomicCAS, duplicates collapse).  The test runs first on the high
+//     word of (f1 + f2) * C2, the sum of the two finalisers' last products
+//     from one multiply chain on the sum of their states, which is within
+//     one of the hash's high word (sketch_core.hpp): a superset of h <= tau,
+//     never a k-mer dropped; the k-mers that pass go to a per-wave LDS queue
+//     whose drain finishes the exact hash, tests it and inserts.  The finalize
 //     kernel sorts the set in LDS, keeps the first s and leaves the set
 //     empty.  When the set holds fewer than s distinct values below tau
 //     (tau < 2^64-1) or overflows, the host moves tau and re-runs the
@@ -35,6 +38,7 @@
 //     distinct hash <= tau is in the set.
 #include "device_util.hpp"
 #include "gg_internal.hpp"
+#include "sketch_core.hpp"
 
 namespace gg {
 namespace {
@@ -92,21 +96,11 @@ __device__ __forceinline__ uint64_t add_rotl31(uint64_t x, uint64_t y) {
   return out;
 }
 
-__device__ __forceinline__ uint64_t fmix_last(uint64_t k) { return k ^ (k >> 33); }
-
-// fmix64 up to its second multiply: fmix64_pre(k) = fmix64_mid(k) * kFmixC2
-constexpr uint64_t kFmixC2 = 0xc4ceb9fe1a85ec53ull;
-__device__ __forceinline__ uint64_t fmix64_mid(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  return k ^ (k >> 33);
-}
-// high word of y * kFmixC2 (mod 2^64) without the low word: one v_mul_hi_u32
-// and two v_mul_lo_u32 instead of a v_mad_u64_u32 and two v_mul_lo_u32
-__device__ __forceinline__ uint32_t hi_times_c2(uint64_t y) {
-  const uint32_t lo = (uint32_t)y, hi = (uint32_t)(y >> 32);
-  return __umulhi(lo, (uint32_t)kFmixC2) + lo * (uint32_t)(kFmixC2 >> 32) + hi * (uint32_t)kFmixC2;
-}
+// the finalisers' tail and the tau prefilter (sketch_core.hpp)
+using sketch::exact_hash;
+using sketch::fmix64_mid;
+using sketch::prefilter_threshold;
+using sketch::prefilter_word;
 
 // h * 5 + c with one v_lshl_add_u64 (hipcc otherwise lowers the multiply by
 // 5 to v_mad_u64_u32 sequences).
@@ -145,7 +139,7 @@ __device__ __forceinline__ uint32_t group_byte(uint32_t hi, uint32_t lo, int q) 
   return (w >> (8 * (3 - (q & 3)))) & 0xFFu;
 }
 
-// murmurhash3_x64_128(bytes, seed).0 = fmix_last(f1) + fmix_last(f2) with
+// murmurhash3_x64_128(bytes, seed).0 = exact_hash(f1, f2) with
 // (f1, f2) from hash_parts, where byte p = ASCII of base p of the
 // k-mer whose MSB-first 2-bit code is top-aligned in `code` (base 0 in bits
 // 63..62; bits below 64-2K are ignored, K <= 32).
@@ -225,7 +219,7 @@ __device__ __forceinline__ void hash_parts(uint64_t code, const uint64_t* __rest
   h2 ^= (uint64_t)K;
   h1 += h2;
   h2 += h1;
-  f1 = fmix64_mid(h1);  // the caller finishes with kFmixC2 (hi_times_c2 / full)
+  f1 = fmix64_mid(h1);  // the caller finishes with kFmixC2 (prefilter_word / exact_hash)
   f2 = fmix64_mid(h2);
 }
 
@@ -368,11 +362,7 @@ struct CandQueue {
   uint32_t head, tail, claim;
 };
 
-__device__ __forceinline__ uint64_t exact_hash(uint64_t f1, uint64_t f2) {
-  return fmix_last(f1 * kFmixC2) + fmix_last(f2 * kFmixC2);
-}
-
-// A k-mer whose high-word sum passed the prefilter: queued with its two
+// A k-mer whose prefilter word passed: queued with its two
 // finaliser states; the drain finishes the hash and inserts it if <= tau.
 __device__ __forceinline__ void queue_push_mid(CandQueue& q, uint64_t f1, uint64_t f2, uint32_t slot_mode,
                                                uint64_t tau, uint64_t* __restrict__ table,
@@ -552,12 +542,13 @@ __global__ __launch_bounds__(kBlock, GG_K1_MIN_WAVES) void sketch_candidates_ker
       rem = run.len - (uint32_t)K + 1u - k0;
       slot = run.genome - a.slot_genome0;
       tau = a.tau[slot];
-      // prefilter on the high words: h = fmix_last(f1) + fmix_last(f2)
-      // has high word S or S + 1 (carry), S = hi(f1) + hi(f2), so h <= tau
-      // needs S <= hi(tau) or S = 2^32 - 1, i.e. S + 1 <= hi(tau) + 1 (mod
-      // 2^32; every S passes when hi(tau) = 2^32 - 1)
-      const uint32_t tau_hi = (uint32_t)(tau >> 32);
-      thr = tau_hi == 0xFFFFFFFFu ? 0xFFFFFFFFu : tau_hi + 1u;
+      // prefilter on one multiply chain: with p_i = f_i * C2, h = L(p1) +
+      // L(p2), L(k) = k ^ (k >> 33), has high word hi(p1) + hi(p2) + c', and
+      // P = (f1 + f2) * C2 = p1 + p2 has hi(p1) + hi(p2) + c'', both carries
+      // 0 or 1: hi(h) - hi(P) is -1, 0 or 1, so h <= tau needs hi(P) in
+      // [-1, hi(tau) + 1], i.e. hi(P) + 1 <= hi(tau) + 2 (mod 2^32; every
+      // k-mer passes when hi(tau) >= 2^32 - 3)
+      thr = prefilter_threshold(tau);
       const uint64_t b = run.base + k0;  // first base of the segment's first k-mer
       wp = a.words + (b >> 4);
       off = (uint32_t)b & 15u;
@@ -602,16 +593,15 @@ __global__ __launch_bounds__(kBlock, GG_K1_MIN_WAVES) void sketch_candidates_ker
         const uint64_t rev = window64<K>(R, RP, t0);
         hash_parts<K>(fwd < rev ? fwd : rev, mtab, seed, f1[j], f2[j]);
       }
-      uint32_t hs[kGroup];  // S + 1 per k-mer
+      uint32_t hs[kGroup];  // hi(P) + 1 per k-mer
 #pragma unroll
-      for (int j = 0; j < kGroup; ++j) hs[j] = hi_times_c2(f1[j]) + hi_times_c2(f2[j]) + 1u;
+      for (int j = 0; j < kGroup; ++j) hs[j] = prefilter_word(f1[j], f2[j]);
       bool any = false;
 #pragma unroll
       for (int j = 0; j < kGroup; ++j) any |= hs[j] <= thr;
       if (any) {
-        // (a lane of the wave has a k-mer whose high-word sum can reach
-        // tau): finish the exact test for the group's k-mers and queue
-        // the candidates
+        // (a lane of the wave has a k-mer whose hash can be <= tau): queue
+        // the group's k-mers that pass; the drain takes the exact test
 #pragma unroll
         for (int j = 0; j < kGroup; ++j) {
           if (hs[j] <= thr && (uint32_t)(g * kGroup + j) < cnt)
