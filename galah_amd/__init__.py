@@ -38,6 +38,7 @@ __all__ = [
     "ani_pairs_host", "validate_clusters_host", "Validation", "ClusterValidation", "validate_clusters",
     "read_clustering_file", "write_cluster_definition", "write_representative_list",
     "pairs_border_host", "PreclusterState", "relabel_pairs", "cluster_update",
+    "ani_matrix_host", "ani_matrix", "write_ani_matrix",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -67,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "gg_pairs_border", "gg_pairs_border_device", "gg_pairs_border_host", "gg_update_files",
     "gg_preclusters", "gg_preclusters_device",
     "gg_ani_f32_device", "gg_cluster_rows_device", "gg_cluster_files_resident",
+    "gg_ani_matrix_host", "gg_ani_matrix", "gg_ani_matrix_device", "gg_ani_matrix_files",
 )
 
 GG_OK = 0
@@ -209,6 +211,22 @@ _sig("gg_cluster_files_resident", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _
 _sig("gg_ani_pairs_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _u64, _vp])
 _sig("gg_ani_pairs", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
 _sig("gg_ani_pairs_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
+
+
+class _MatrixSummary(ctypes.Structure):
+    _fields_ = [("n_entries", ctypes.c_uint64), ("n_columns", ctypes.c_uint64), ("column_entries", ctypes.c_uint64),
+                ("ani_rechecked", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+_sig("gg_ani_matrix_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _u32, _vp, _vp, _vp])
+_sig("gg_ani_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, ctypes.POINTER(_MatrixSummary)])
+_sig("gg_ani_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, ctypes.POINTER(_MatrixSummary),
+                                    _vp])
+_sig("gg_ani_matrix_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp, _vp,
+                                   ctypes.POINTER(_MatrixSummary)])
 
 
 class _Validation(ctypes.Structure):
@@ -485,6 +503,34 @@ def ani_pairs_host(sketches, lens, pairs, k=21):
     if st != GG_OK:
         raise _thread_err(st)
     return p, ani[:len(p)]
+
+
+def _matrix_rows_arg(rows, n):
+    """(rows u32 or None, its pointer, m) of a list of row indices; None: rows 0 .. n-1."""
+    if rows is None:
+        return None, None, n
+    r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    return r, _ptr(r), len(r)
+
+
+def _matrix_out(m):
+    z = max(m, 1)
+    return np.zeros((z, z), np.uint32), np.zeros((z, z), np.uint32), np.zeros((z, z), np.float32)
+
+
+def ani_matrix_host(sketches, lens, rows=None, k=21):
+    """The dense matrix of the rows listed (rows=None: all of them, in order):
+    finch's merge counts and the stored f32 ANI of every two of them
+    (gg_ani_matrix_host: the merge itself, no device) -> (common u32, total
+    u32, ani f32), each [m, m].  Any order, a row may be listed more than
+    once; the diagonal holds (len, len, 1.0), an empty row (0, 0, 0.0)."""
+    sk, ln, n, s = _rows_arg(sketches, lens)
+    r, rp, m = _matrix_rows_arg(rows, n)
+    common, total, ani = _matrix_out(m)
+    st = _L.gg_ani_matrix_host(_ptr(sk), _ptr(ln), n, s, k, rp, m, _ptr(common), _ptr(total), _ptr(ani))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return common[:m, :m], total[:m, :m], ani[:m, :m]
 
 
 def pairs_border_host(sketches, lens, n_old, min_ani, k=21):
@@ -1054,6 +1100,33 @@ class Context:
             raise self._err(st)
         return p, ani[:len(p)]
 
+    def ani_matrix(self, sketches, lens, rows=None):
+        """ani_matrix_host on the context's (first) device: the shared-hash
+        counts as one product on the matrix cores ->
+        (common, total, ani, summary dict of gg_matrix_summary)."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        r, rp, m = _matrix_rows_arg(rows, n)
+        common, total, ani = _matrix_out(m)
+        summary = _MatrixSummary()
+        st = _L.gg_ani_matrix(self._c, _ptr(sk), _ptr(ln), n, rp, m, _ptr(common), _ptr(total), _ptr(ani),
+                              ctypes.byref(summary))
+        if st != GG_OK:
+            raise self._err(st)
+        return common[:m, :m], total[:m, :m], ani[:m, :m], summary.as_dict()
+
+    def ani_matrix_files(self, paths, cache_dir=None):
+        """sketch_files(paths, cache_dir) followed by ani_matrix over all rows
+        (gg_ani_matrix_files) -> (common, total, ani, summary dict)."""
+        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        m = len(paths)
+        common, total, ani = _matrix_out(m)
+        summary = _MatrixSummary()
+        st = _L.gg_ani_matrix_files(self._c, arr, m, os.fsencode(cache_dir) if cache_dir else None, _ptr(common),
+                                    _ptr(total), _ptr(ani), ctypes.byref(summary))
+        if st != GG_OK:
+            raise self._err(st)
+        return common[:m, :m], total[:m, :m], ani[:m, :m], summary.as_dict()
+
     def validate_clusters(self, sketches, lens, clusters, ani):
         """validate_clusters_host on the device (gg_validate_clusters): the
         members through the named-pair kernel, the representatives through
@@ -1253,6 +1326,24 @@ class Context:
                                     None if stream is None else stream)
         if st != GG_OK:
             raise self._err(st)
+
+    def ani_matrix_device(self, d_sketches, d_lens, n, d_rows, m, d_common=None, d_total=None, d_ani=None,
+                          stream=None):
+        """ani_matrix over device-resident tensors: d_sketches [n, s] u64,
+        d_lens [n] u32 (as i32 tensors), d_rows [m] row indices or None
+        (positions are rows 0 .. m-1); d_common / d_total (i32) / d_ani (f32),
+        each [m, m] or None, are written.  An index >= n is an empty row.
+        Synchronises the stream -> summary dict."""
+        summary = _MatrixSummary()
+        st = _L.gg_ani_matrix_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n,
+                                     None if d_rows is None else _dev_ptr(d_rows), m,
+                                     None if d_common is None else _dev_ptr(d_common),
+                                     None if d_total is None else _dev_ptr(d_total),
+                                     None if d_ani is None else _dev_ptr(d_ani), ctypes.byref(summary),
+                                     None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+        return summary.as_dict()
 
     def synth_mixed_device(self, lens, cluster_size, max_sub_rate, n_run_rate, seed, d_words, stream=None,
                            first_genome=0):
@@ -1700,6 +1791,31 @@ def rust_f32(x):
     """Rust's `{}` of an f32: the shortest round-trip digits, no exponent, no
     trailing ".0"."""
     return np.format_float_positional(np.float32(x), unique=True, trim="-")
+
+
+def ani_matrix(genomes, num_kmers=1000, kmer_length=21, sketch_cache_dir=None):
+    """The finch ANI between every two of the genomes (paths): each file
+    sketched once (from sketch_cache_dir when it has it), then one dense
+    matrix call on the GPU -> an [N, N] float32 array, symmetric, the value
+    galah stores for each pair (1.0 on the diagonal of a non-empty genome)."""
+    genomes = list(genomes)
+    if not genomes:
+        return np.zeros((0, 0), np.float32)
+    ctx = _context(kmer_length, num_kmers)
+    _, _, ani, _ = ctx.ani_matrix_files(genomes, cache_dir=sketch_cache_dir)
+    return ani
+
+
+def write_ani_matrix(f, genomes, ani):
+    """The matrix as a TSV: a header row of the genomes' names (after an
+    empty corner cell), then one row per genome, its name and its values as
+    Rust prints an f32 (rust_f32).  f: a file object (text or binary) or a
+    path."""
+    ani = np.asarray(ani, dtype=np.float32)
+    if ani.shape != (len(genomes), len(genomes)):
+        raise ValueError("ani must be [len(genomes), len(genomes)]")
+    head = ["\t".join([""] + [str(g) for g in genomes]) + "\n"]
+    _write_lines(f, head + ["\t".join([str(g)] + [rust_f32(v) for v in row]) + "\n" for g, row in zip(genomes, ani)])
 
 
 class ClusterValidation(Validation):

@@ -1,0 +1,557 @@
+// The dense ANI matrix of a set of rows: for m listed rows
+// of a sketch matrix, common / total / f32 ANI of every two of them, [m x m],
+// by the rules of matrix_core.hpp.  common is a contraction: with the 0/1
+// incidence matrix A [positions x columns], common = A A^T, on the i8 matrix
+// instruction.
+//
+//   mx_offsets_kernel  one workgroup: every position's row, length and the
+//                      exclusive sum of the lengths.
+//   mx_keys_kernel     (hash, slot = position * s + e) of every entry, the
+//                      valid ones packed to the front, the others (key ~0)
+//                      behind them, so the sort's count needs no read-back.
+//   hipcub SortPairs   on the 64-bit key (stable: the padding stays behind).
+//   mx_flags_kernel    the column rule on the sorted keys, both flags packed;
+//   hipcub InclusiveSum  column ids and, at the end, the two counts.
+//   mx_ids_kernel      the id (or none) of every entry, scattered to its slot.
+//   mx_pieces_kernel   one workgroup per position: its kept ids compacted in
+//                      order into a contiguous piece with a count.
+//   [read back: entries, columns, column entries -- the one sync before the product]
+//   mx_common_kernel   the product and the epilogue, below.
+//
+// mx_common_kernel: one workgroup (4 waves) per tile pair ti <= tj of 64 x 64
+// positions, K over the columns in chunks of 512.  Per chunk: one thread per
+// row finds the row's cursor (a binary search of its piece from the last
+// cursor) and its next id, a wave minimum per tile gives the chunk to run --
+// chunks in which either tile holds nothing are jumped over; the workgroup
+// clears the two [64 x 512] byte images (one for a diagonal tile), every wave
+// takes rows in turn and its 64 lanes scatter the row's entries of the chunk
+// (64 ids per step from the cursor); after the barrier wave w reads the A
+// fragments of rows 16 w .. 16 w + 15 and the B fragments of the four 16-row
+// blocks of the other tile and issues mfma_i32_16x16x64_i8, 8 k-steps x 4
+// blocks, into four i32x4 accumulators that live across the chunks.
+// Epilogue per element: total by the rank rule from the two rows in global
+// memory, the ANI by ani::value with the device log, stores at (a, b) and
+// (b, a); a diagonal tile writes a <= b only.  LDS: 2 x 33,792 B images +
+// 3,080 B of row state = 70,664 B, two workgroups per CU.
+//
+// No workgroup waits for another, the kernels are not persistent, and the
+// only atomic is the flagged list's counter (ani_flag.hpp).  The kernels are
+// launched plainly (no gg_timing_read slot).
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ani_core.hpp"
+#include "ani_flag.hpp"
+#include "context.hpp"
+#include "device_util.hpp"
+#include "gg_internal.hpp"
+#include "matrix_core.hpp"
+
+namespace gg {
+namespace {
+
+using matrix::kChunk;
+using matrix::kNoColumn;
+using matrix::kRowBytes;
+using matrix::kTile;
+using matrix::kTileBytes;
+
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;
+constexpr uint32_t kOffBlock = 1024;
+constexpr uint32_t kOffPer = matrix::kMaxRows / kOffBlock;  // positions per thread of mx_offsets_kernel
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+inline dim3 grid_for(uint64_t items) { return dim3((uint32_t)std::min<uint64_t>(16384, (items + 255) / 256)); }
+
+// pos_row[a] (kNoRow: an index >= n, an empty row), pos_len[a], pos_off[0 .. m] the exclusive sum of the lengths
+__global__ __launch_bounds__(kOffBlock) void mx_offsets_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
+                                                               const uint32_t* __restrict__ rows, uint32_t m,
+                                                               uint32_t* __restrict__ pos_row,
+                                                               uint32_t* __restrict__ pos_len,
+                                                               uint32_t* __restrict__ pos_off) {
+  __shared__ uint32_t part[kOffBlock];
+  const uint32_t t = threadIdx.x, a0 = t * kOffPer;
+  uint32_t sum = 0;
+  for (uint32_t a = a0; a < min(a0 + kOffPer, m); ++a) {
+    const uint32_t g = rows ? rows[a] : a;
+    const bool ok = g < n;
+    const uint32_t len = ok ? min(lens[g], s) : 0u;
+    pos_row[a] = ok ? g : kNoRow;
+    pos_len[a] = len;
+    sum += len;
+  }
+  part[t] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < kOffBlock; d <<= 1) {  // inclusive sum of the partial sums
+    const uint32_t v = t >= d ? part[t - d] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t off = part[t] - sum;
+  for (uint32_t a = a0; a < min(a0 + kOffPer, m); ++a) {
+    pos_off[a] = off;
+    off += pos_len[a];
+  }
+  if (t == kOffBlock - 1) pos_off[m] = part[t];
+}
+
+__global__ __launch_bounds__(256) void mx_keys_kernel(const uint64_t* __restrict__ sk, uint32_t s, uint32_t m,
+                                                      const uint32_t* __restrict__ pos_row,
+                                                      const uint32_t* __restrict__ pos_len,
+                                                      const uint32_t* __restrict__ pos_off,
+                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const uint32_t N = m * s, ne = pos_off[m];
+  for (uint32_t slot = blockIdx.x * 256 + threadIdx.x; slot < N; slot += gridDim.x * 256) {
+    const uint32_t a = slot / s, e = slot - a * s;
+    const uint32_t len = pos_len[a], off = pos_off[a];
+    if (e < len) {
+      keys[off + e] = sk[(uint64_t)pos_row[a] * s + e];
+      vals[off + e] = slot;
+    } else {
+      const uint32_t at = ne + (a * s - off) + (e - len);  // the slots without an entry, in slot order
+      keys[at] = ~0ull;
+      vals[at] = kNoColumn;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void mx_flags_kernel(const uint64_t* __restrict__ K, uint32_t N,
+                                                       const uint32_t* __restrict__ pos_off, uint32_t m,
+                                                       uint64_t* __restrict__ flags) {
+  const uint32_t ne = pos_off[m];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
+    flags[i] = i < ne ? matrix::column_flags(K, i, ne) : 0ull;
+}
+
+__global__ __launch_bounds__(256) void mx_ids_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ slot_of,
+                                                     const uint64_t* __restrict__ sums,
+                                                     const uint32_t* __restrict__ pos_off, uint32_t m,
+                                                     uint32_t* __restrict__ id_of) {
+  const uint32_t ne = pos_off[m];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256)
+    id_of[slot_of[i]] = matrix::in_column(K, i, ne) ? matrix::column_id(sums[i]) : kNoColumn;
+}
+
+// piece[a * s ..) the ids of position a's entries that lie in a column, in the row's order; piece_cnt[a]
+__global__ __launch_bounds__(256) void mx_pieces_kernel(const uint32_t* __restrict__ id_of,
+                                                        const uint32_t* __restrict__ pos_len, uint32_t s,
+                                                        uint32_t* __restrict__ piece, uint32_t* __restrict__ piece_cnt) {
+  __shared__ uint32_t wave_cnt[4];
+  const uint32_t a = blockIdx.x, len = pos_len[a], lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t* in = id_of + (uint64_t)a * s;
+  uint32_t* out = piece + (uint64_t)a * s;
+  uint32_t done = 0;
+  for (uint32_t base = 0; base < len; base += 256) {  // (len is the workgroup's: whole waves reach the ballot)
+    const uint32_t e = base + threadIdx.x;
+    const uint32_t id = e < len ? in[e] : kNoColumn;
+    const bool keep = id != kNoColumn;
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t at = done;
+    for (uint32_t w = 0; w < wave; ++w) at += wave_cnt[w];
+    if (keep) out[at + lanes_below(mask)] = id;
+    done += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) piece_cnt[a] = done;
+}
+
+struct MxLaunch {
+  const uint64_t* sk;
+  uint32_t s, m;
+  const uint32_t* pos_row;
+  const uint32_t* pos_len;
+  const uint32_t* piece;
+  const uint32_t* piece_cnt;
+  uint32_t* common;
+  uint32_t* total;
+  float* ani;
+  int k;
+  double E;
+  AniFlagged* list;
+  uint64_t cap;
+  unsigned long long* count;
+};
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+  for (int d = 32; d; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d));
+  return v;
+}
+
+__global__ __launch_bounds__(256) void mx_common_kernel(MxLaunch a) {
+  __shared__ __align__(16) uint8_t image[2 * kTileBytes];
+  __shared__ uint64_t s_last[2 * kTile];
+  __shared__ uint32_t s_row[2 * kTile], s_len[2 * kTile], s_cnt[2 * kTile], s_cur[2 * kTile];
+  __shared__ uint32_t s_min[2];
+  const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  uint32_t ti, tj;
+  matrix::tile_pair_of(blockIdx.x, &ti, &tj);
+  const bool diag = ti == tj;
+  const uint32_t sides = diag ? 1u : 2u;
+  // rows 0 .. 63 of the state are tile ti's positions, 64 .. 127 tile tj's (not filled for a diagonal tile)
+  if (t < sides * kTile) {
+    const uint32_t pos = (t < kTile ? ti : tj) * kTile + (t & (kTile - 1));
+    const bool ok = pos < a.m;
+    const uint32_t row = ok ? a.pos_row[pos] : kNoRow;
+    const uint32_t len = ok ? a.pos_len[pos] : 0u;
+    s_row[t] = row;
+    s_len[t] = len;
+    s_cnt[t] = ok ? a.piece_cnt[pos] : 0u;
+    s_cur[t] = 0;
+    s_last[t] = len ? a.sk[(uint64_t)row * a.s + len - 1] : 0ull;
+  }
+  __syncthreads();
+
+  i32x4 acc[4];
+  for (int nb = 0; nb < 4; ++nb) acc[nb] = i32x4{0, 0, 0, 0};
+  const uint8_t* img_a = image;
+  const uint8_t* img_b = image + (diag ? 0u : kTileBytes);
+  uint32_t k0 = 0;  // (every branch on k0, s_min is the workgroup's)
+  for (;;) {
+    if (t < 2 * kTile) {  // waves 0 and 1: a tile each
+      uint32_t next = kNoColumn;
+      if (t < sides * kTile) {
+        const uint32_t pos = (t < kTile ? ti : tj) * kTile + (t & (kTile - 1));
+        const uint32_t cnt = s_cnt[t];
+        const uint32_t* pc = a.piece + (uint64_t)pos * a.s;  // (not read when cnt == 0)
+        const uint32_t cur = matrix::cursor_at(pc, s_cur[t], cnt, k0);
+        s_cur[t] = cur;
+        if (cur < cnt) next = pc[cur];
+      }
+      next = wave_min(next);
+      if (lane == 0) s_min[wave] = next;
+    }
+    __syncthreads();
+    const uint32_t kc = matrix::next_chunk(s_min[0], diag ? s_min[0] : s_min[1]);
+    if (kc == kNoColumn) break;
+    if (kc != k0) {  // a chunk (or more) in which a tile holds nothing: jump, find the cursors there
+      k0 = kc;
+      __syncthreads();
+      continue;
+    }
+    for (uint32_t i = t; i < sides * kTileBytes / 16; i += 256) reinterpret_cast<uint4*>(image)[i] = uint4{0, 0, 0, 0};
+    __syncthreads();
+    for (uint32_t r = wave; r < sides * kTile; r += 4) {
+      const uint32_t pos = (r < kTile ? ti : tj) * kTile + (r & (kTile - 1));
+      const uint32_t cnt = s_cnt[r];
+      const uint32_t* pc = a.piece + (uint64_t)pos * a.s;
+      uint8_t* img = image + (r < kTile ? 0u : kTileBytes);
+      for (uint32_t e = s_cur[r] + lane;; e += 64) {  // (s_cur[r], cnt are the wave's)
+        bool in = e < cnt;
+        uint32_t col = 0;
+        if (in) {
+          col = pc[e] - k0;
+          in = col < kChunk;
+        }
+        if (in) img[matrix::image_offset(r & (kTile - 1), col)] = 1;
+        if (__ballot(in) != ~0ull) break;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t ks = 0; ks < matrix::kKSteps; ++ks) {
+      const i32x4 af = *reinterpret_cast<const i32x4*>(img_a + matrix::fragment_offset(lane, ks, wave));
+#pragma unroll
+      for (uint32_t nb = 0; nb < 4; ++nb) {
+        const i32x4 bf = *reinterpret_cast<const i32x4*>(img_b + matrix::fragment_offset(lane, ks, nb));
+        acc[nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, acc[nb], 0, 0, 0);
+      }
+    }
+    k0 += kChunk;
+    __syncthreads();
+  }
+
+  // epilogue: wave w holds rows 16 w .. 16 w + 15 of tile ti against the 64 positions of tile tj
+  const uint32_t sb = diag ? 0u : kTile;  // tile tj's row state
+#pragma unroll
+  for (uint32_t nb = 0; nb < 4; ++nb) {
+#pragma unroll
+    for (uint32_t reg = 0; reg < 4; ++reg) {
+      const uint32_t ra = wave * 16 + matrix::cd_row(lane, reg), rb = nb * 16 + matrix::cd_col(lane);
+      const uint32_t pa = ti * kTile + ra, pb = tj * kTile + rb;
+      const bool live = pa < a.m && pb < a.m && (!diag || pa <= pb);
+      uint32_t common = 0, total = 0;
+      bool flagged = false;
+      if (live) {
+        const uint32_t ga = s_row[ra], gb = s_row[sb + rb];
+        matrix::cell_counts(pa == pb || ga == gb, a.sk + (uint64_t)ga * a.s, s_len[ra], s_last[ra],
+                            a.sk + (uint64_t)gb * a.s, s_len[sb + rb], s_last[sb + rb], (uint32_t)acc[nb][reg], &common,
+                            &total);
+        const uint64_t ab = (uint64_t)pa * a.m + pb, ba = (uint64_t)pb * a.m + pa;
+        if (a.common) {
+          a.common[ab] = common;
+          a.common[ba] = common;
+        }
+        if (a.total) {
+          a.total[ab] = total;
+          a.total[ba] = total;
+        }
+        if (a.ani) {
+          const ani::Value v = ani::value(common, total, a.k, a.E, DeviceLog{});
+          a.ani[ab] = v.f;
+          a.ani[ba] = v.f;
+          flagged = v.flagged;
+        }
+      }
+      // (a * m + b < 2^30; a flagged cell is off the diagonal, a < b or of an off-diagonal tile)
+      if (a.ani) ani_flag_push(flagged, pa * a.m + pb, common, total, a.list, a.cap, a.count);
+    }
+  }
+}
+
+}  // namespace
+
+gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
+                            uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
+                            hipStream_t st) {
+  if (sum) *sum = gg_matrix_summary{};
+  if (m == 0) return GG_OK;
+  const uint32_t s = c->s;
+  const uint64_t N64 = (uint64_t)m * s;
+  if (N64 >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, "gg_ani_matrix: 2^31 sketch slots or more");
+  const uint32_t N = (uint32_t)N64;
+  uint32_t *pos_row, *pos_len, *pos_off, *vals_in, *vals_out, *piece, *piece_cnt;
+  uint64_t *keys_in, *keys_out, *sums, *h_back;
+  GG_HIP(c, scratch_t(c, "mx_pos", (size_t)4 * m + 1, &pos_row));
+  pos_len = pos_row + m;
+  piece_cnt = pos_len + m;
+  pos_off = piece_cnt + m;
+  GG_HIP(c, scratch_t(c, "mx_keys_in", (size_t)N, &keys_in));
+  GG_HIP(c, scratch_t(c, "mx_keys_out", (size_t)N, &keys_out));
+  GG_HIP(c, scratch_t(c, "mx_sums", (size_t)N, &sums));
+  GG_HIP(c, scratch_t(c, "mx_vals_in", (size_t)N, &vals_in));
+  GG_HIP(c, scratch_t(c, "mx_vals_out", (size_t)N, &vals_out));
+  GG_HIP(c, scratch_t(c, "mx_piece", (size_t)N, &piece));
+  GG_HIP(c, host_scratch_t(c, "mx_back", 2, &h_back));
+  size_t sort_bytes = 0, scan_bytes = 0;
+  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, 64));
+  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N));
+  const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+  uint8_t* tmp;
+  GG_HIP(c, scratch_t(c, "mx_tmp", std::max<size_t>(tmp_bytes, 1), &tmp));
+
+  hipLaunchKernelGGL(mx_offsets_kernel, dim3(1), dim3(kOffBlock), 0, st, d_lens, n, s, d_rows, m, pos_row, pos_len,
+                     pos_off);
+  GG_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(mx_keys_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, m, pos_row, pos_len, pos_off, keys_in,
+                     vals_in);
+  GG_HIP(c, hipGetLastError());
+  size_t bytes = tmp_bytes;
+  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
+                                               vals_out, (int)N, 0, 64, st));
+  uint64_t* flags = keys_in;  // (the sort's input is free)
+  uint32_t* id_of = vals_in;
+  hipLaunchKernelGGL(mx_flags_kernel, grid_for(N), dim3(256), 0, st, keys_out, N, pos_off, m, flags);
+  GG_HIP(c, hipGetLastError());
+  bytes = tmp_bytes;
+  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
+  hipLaunchKernelGGL(mx_ids_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, sums, pos_off, m, id_of);
+  GG_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(mx_pieces_kernel, dim3(m), dim3(256), 0, st, id_of, pos_len, s, piece, piece_cnt);
+  GG_HIP(c, hipGetLastError());
+  // entries, columns, column entries: the one read-back before the product
+  GG_HIP(c, hipMemcpyAsync(&h_back[0], sums + (N - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  GG_HIP(c, hipMemcpyAsync(&h_back[1], pos_off + m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  GG_HIP(c, hipStreamSynchronize(st));
+  const uint64_t n_columns = (uint32_t)h_back[0], column_entries = h_back[0] >> 32, n_entries = (uint32_t)h_back[1];
+  if (n_entries > N || column_entries > n_entries || 2 * n_columns > column_entries)
+    return fail(c, GG_ERR_INTERNAL, "gg_ani_matrix: bad column counts");
+
+  MxLaunch a{d_sk, s, m, pos_row, pos_len, piece, piece_cnt, d_common, d_total, d_ani, c->k, 0.0, nullptr, 0, nullptr};
+  const dim3 grid(matrix::tile_pairs_of(matrix::tiles_of(m)));
+  uint64_t flagged = 0;
+  if (d_ani) {
+    const gg_status r = ani_flagged_passes(
+        c, "gg_ani_matrix", (uint64_t)m * m,
+        [&](double E, AniFlagged* list, uint64_t cap, unsigned long long* count) {
+          a.E = E;
+          a.list = list;
+          a.cap = cap;
+          a.count = count;
+          hipLaunchKernelGGL(mx_common_kernel, grid, dim3(256), 0, st, a);
+          return hipGetLastError();
+        },
+        d_ani, nullptr, m, &flagged, st);
+    if (r != GG_OK) return r;
+  } else {
+    hipLaunchKernelGGL(mx_common_kernel, grid, dim3(256), 0, st, a);
+    GG_HIP(c, hipGetLastError());
+    GG_HIP(c, hipStreamSynchronize(st));
+  }
+  if (sum) {
+    sum->n_entries = n_entries;
+    sum->n_columns = n_columns;
+    sum->column_entries = column_entries;
+    sum->ani_rechecked = 2 * flagged;  // cells: the matrix mirrors each listed entry
+  }
+  return GG_OK;
+}
+
+namespace {
+
+// the checks of the host-input forms (the message goes to `err`)
+gg_status check_matrix_input(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                             uint32_t sketch_size, int k, const uint32_t* rows, uint32_t m, const void* common,
+                             const void* total, const void* ani, std::string& err) {
+  if (k < 1 || k > 32 || sketch_size < 1) {
+    err = w + ": kmer_length must be 1..32 and sketch_size at least 1";
+    return GG_ERR_INVALID_ARG;
+  }
+  if (m > matrix::kMaxRows) {
+    err = w + ": more than 32768 rows listed";
+    return GG_ERR_INVALID_ARG;
+  }
+  if (m == 0) return GG_OK;
+  if (!common && !total && !ani) {
+    err = w + ": no output asked for";
+    return GG_ERR_INVALID_ARG;
+  }
+  if (n && (!sketches || !lens)) {
+    err = w + ": null argument";
+    return GG_ERR_INVALID_ARG;
+  }
+  if (!rows && m > n) {
+    err = w + ": more positions than rows";
+    return GG_ERR_INVALID_ARG;
+  }
+  for (uint32_t g = 0; g < n; ++g)
+    if (lens[g] > sketch_size) {
+      err = w + ": sketch longer than sketch_size";
+      return GG_ERR_INVALID_ARG;
+    }
+  for (uint32_t a = 0; rows && a < m; ++a)
+    if (rows[a] >= n) {
+      err = w + ": row index out of range";
+      return GG_ERR_INVALID_ARG;
+    }
+  return GG_OK;
+}
+
+gg_status ani_matrix_ctx(gg_ctx* pm, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
+                         uint32_t m, uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary) {
+  std::string err;
+  const gg_status chk = check_matrix_input("gg_ani_matrix", sketches, lens, n, pm->s, pm->k, rows, m, common, total, ani,
+                                           err);
+  if (chk != GG_OK) return fail(pm, chk, err);
+  if (m == 0) return GG_OK;
+  if (hipSetDevice(pm->device) != hipSuccess) return fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  const size_t cells = (size_t)m * m;
+  uint64_t* d_sk = nullptr;
+  uint32_t *d_len = nullptr, *d_rows = nullptr, *d_common = nullptr, *d_total = nullptr;
+  float* d_ani = nullptr;
+  GG_HIP(pm, scratch_t(pm, "mx_h_sk", (size_t)n * pm->s, &d_sk));
+  GG_HIP(pm, scratch_t(pm, "mx_h_len", (size_t)n, &d_len));
+  GG_HIP(pm, hipMemcpyAsync(d_sk, sketches, (size_t)n * pm->s * sizeof(uint64_t), hipMemcpyHostToDevice, pm->stream));
+  GG_HIP(pm, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
+  if (rows) {
+    GG_HIP(pm, scratch_t(pm, "mx_h_rows", (size_t)m, &d_rows));
+    GG_HIP(pm, hipMemcpyAsync(d_rows, rows, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
+  }
+  if (common) GG_HIP(pm, scratch_t(pm, "mx_h_common", cells, &d_common));
+  if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", cells, &d_total));
+  if (ani) GG_HIP(pm, scratch_t(pm, "mx_h_ani", cells, &d_ani));
+  const gg_status st = ani_matrix_device(pm, d_sk, d_len, n, d_rows, m, d_common, d_total, d_ani, summary, pm->stream);
+  if (st != GG_OK) return st;
+  if (common) GG_HIP(pm, hipMemcpyAsync(common, d_common, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  if (total) GG_HIP(pm, hipMemcpyAsync(total, d_total, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  if (ani) GG_HIP(pm, hipMemcpyAsync(ani, d_ani, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  GG_HIP(pm, hipStreamSynchronize(pm->stream));
+  return GG_OK;
+}
+
+}  // namespace
+}  // namespace gg
+
+using namespace gg;
+
+extern "C" {
+
+gg_status gg_ani_matrix_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                             int kmer_length, const uint32_t* rows, uint32_t m, uint32_t* common, uint32_t* total,
+                             float* ani) {
+  std::string err;
+  const gg_status st = check_matrix_input("gg_ani_matrix_host", sketches, lens, n, sketch_size, kmer_length, rows, m,
+                                          common, total, ani, err);
+  if (st != GG_OK) {
+    set_thread_error(err);
+    return st;
+  }
+  // the merge itself per unordered pair (a row against itself gives its length twice), mirrored
+  for (uint32_t a = 0; a < m; ++a) {
+    const uint32_t ga = rows ? rows[a] : a;
+    for (uint32_t b = a; b < m; ++b) {
+      const uint32_t gb = rows ? rows[b] : b;
+      uint32_t c, t;
+      validate::merge_counts(sketches + (size_t)ga * sketch_size, lens[ga], sketches + (size_t)gb * sketch_size, lens[gb],
+                             &c, &t);
+      const size_t ab = (size_t)a * m + b, ba = (size_t)b * m + a;
+      if (common) common[ab] = common[ba] = c;
+      if (total) total[ab] = total[ba] = t;
+      if (ani) ani[ab] = ani[ba] = (float)ani_f64(c, t, kmer_length);
+    }
+  }
+  return GG_OK;
+}
+
+gg_status gg_ani_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
+                        uint32_t m, uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  gg_ctx* pm = primary(ctx);
+  if (summary) *summary = gg_matrix_summary{};
+  const gg_status st = ani_matrix_ctx(pm, sketches, lens, n, rows, m, common, total, ani, summary);
+  if (st != GG_OK) {
+    if (summary) *summary = gg_matrix_summary{};
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
+}
+
+gg_status gg_ani_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                               const uint32_t* d_rows, uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani,
+                               gg_matrix_summary* summary, void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  gg_ctx* pm = primary(ctx);
+  gg_status st = GG_OK;
+  if (summary) *summary = gg_matrix_summary{};
+  if (m > matrix::kMaxRows)
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_device: more than 32768 rows listed");
+  else if (m && !d_common && !d_total && !d_ani)
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_device: no output asked for");
+  else if (m && n && (!d_sketches || !d_lens))
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_device: null buffer");
+  else if (hipSetDevice(pm->device) != hipSuccess)
+    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  else
+    st = ani_matrix_device(pm, d_sketches, d_lens, n, d_rows, m, d_common, d_total, d_ani, summary, (hipStream_t)stream);
+  if (st != GG_OK) {
+    if (summary) *summary = gg_matrix_summary{};
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
+}
+
+gg_status gg_ani_matrix_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, const char* cache_dir,
+                              uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  if (summary) *summary = gg_matrix_summary{};
+  if (n_paths && !paths) return fail(ctx, GG_ERR_INVALID_ARG, "gg_ani_matrix_files: null argument");
+  if (n_paths > matrix::kMaxRows) return fail(ctx, GG_ERR_INVALID_ARG, "gg_ani_matrix_files: more than 32768 files");
+  if (n_paths && !common && !total && !ani)
+    return fail(ctx, GG_ERR_INVALID_ARG, "gg_ani_matrix_files: no output asked for");
+  const uint32_t s = primary(ctx)->s;
+  std::vector<uint64_t> sk((size_t)std::max<uint32_t>(n_paths, 1) * s);
+  std::vector<uint32_t> lens(std::max<uint32_t>(n_paths, 1));
+  const gg_status st = gg_sketch_files(ctx, paths, n_paths, cache_dir, sk.data(), lens.data(), nullptr);
+  if (st != GG_OK) return st;
+  return gg_ani_matrix(ctx, sk.data(), lens.data(), n_paths, nullptr, n_paths, common, total, ani, summary);
+}
+
+}  // extern "C"

@@ -259,6 +259,25 @@ gg_status preclusters_device(gg_ctx* c, uint32_t n, const gg_pair* d_pairs, uint
 // Synchronises st.
 gg_status ani_f32_device(gg_ctx* c, const gg_pair* d_pairs, uint64_t n_pairs, float* d_ani, double* d_ani_f64,
                          uint64_t* n_rechecked, hipStream_t st);
+// The host side of the flagged list behind it, for any kernel that computes
+// ani::value per item (ani_flag.hpp): produce(E, list, cap, count) enqueues
+// the kernel on st, which writes the f32 of every item and appends the
+// flagged ones; it is run once, and once more at the exact count when the
+// list was too small.  The flagged entries are then recomputed with the
+// host's log and patched into d_ani (and d_ani_f64, may be null) at their
+// index; mirror_m != 0: d_ani is an [mirror_m x mirror_m] matrix and the
+// cell across the diagonal is patched too.  *n_flagged (may be null) the
+// list's length.  Synchronises st.
+struct AniFlagged;
+using AniProducer = std::function<hipError_t(double E, AniFlagged* list, uint64_t cap, unsigned long long* count)>;
+gg_status ani_flagged_passes(gg_ctx* c, const char* who, uint64_t n_items, const AniProducer& produce, float* d_ani,
+                             double* d_ani_f64, uint32_t mirror_m, uint64_t* n_flagged, hipStream_t st);
+// The dense matrix of m listed rows (ani_matrix.hip, by matrix_core.hpp):
+// common / total / ani [m x m], each may be null; d_rows null: positions are
+// rows 0 .. m-1.  Synchronises st.
+gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
+                            uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
+                            hipStream_t st);
 // Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
 // ani_f32_device, cluster_device; with sum, the partition of
 // preclusters_device.  *d_pairs / *d_ani (may be null) receive the scratch

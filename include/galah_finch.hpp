@@ -440,6 +440,28 @@ inline ClusterValidation validate_clusters(const std::string& clustering_file, f
   return out;
 }
 
+// The finch ANI between every two of the genomes, as the value galah stores
+// for a pair (gg_ani_matrix_files): every file sketched once, then one dense
+// matrix call on the GPU.  Row-major [N x N], symmetric, 1 on the diagonal of
+// a genome with a non-empty sketch.
+inline std::vector<float> ani_matrix(const std::vector<std::string>& paths, size_t num_kmers = 1000,
+                                     uint8_t kmer_length = 21, const char* sketch_cache_dir = nullptr) {
+  std::vector<float> out(paths.size() * paths.size());
+  if (paths.empty()) return out;
+  std::vector<const char*> c_paths;
+  for (const auto& p : paths) c_paths.push_back(p.c_str());
+  gg_status st = GG_OK;
+  gg_ctx* ctx = gg_create_multi(kmer_length, (uint32_t)num_kmers, 0, nullptr, 0, &st);
+  if (!ctx) throw std::runtime_error(std::string("Failed to sketch genomes with finch: ") + gg_thread_last_error());
+  gg_set_host_threads(ctx, current_num_threads());
+  st = gg_ani_matrix_files(ctx, c_paths.data(), (uint32_t)c_paths.size(), sketch_cache_dir, nullptr, nullptr,
+                           out.data(), nullptr);
+  const std::string msg = st != GG_OK ? gg_last_error(ctx) : "";
+  gg_destroy(ctx);
+  if (st != GG_OK) throw std::runtime_error("Failed to sketch genomes with finch: " + msg);  // src/finch.rs:50
+  return out;
+}
+
 // src/genome_stats.rs:4-9 (#[derive(Debug, PartialEq)])
 struct GenomeAssemblyStats {
   size_t num_contigs;

@@ -571,6 +571,51 @@ gg_status gg_validate_files(gg_ctx* ctx, const char* const* paths, uint32_t n_pa
                             const uint32_t* offsets, uint32_t n_clusters, float ani, const char* cache_dir,
                             gg_validation* sum, gg_pair** bad, float** bad_ani, uint64_t* n_bad);
 
+/* ---- dense ANI matrix of a set of rows ------------------ */
+/* The finch ANI between every two genomes of a set -- the members of one
+ * precluster or species, the representatives of a run -- as an [m x m]
+ * matrix instead of a pair list: for a heatmap, a hierarchical clustering,
+ * or to choose a threshold.  The shared-hash count of every two rows is the
+ * product A A^T of the rows' 0/1 incidence matrix over the distinct hashes
+ * that two or more of them hold, computed on the matrix cores (i8);
+ * galah_amd/csrc/matrix_core.hpp states the rules.  No threshold, no gate:
+ * every cell is exact. */
+typedef struct gg_matrix_summary {
+  uint64_t n_entries;      /* sketch entries of the listed rows */
+  uint64_t n_columns;      /* distinct hashes held at >= 2 listed positions */
+  uint64_t column_entries; /* entries that fall in a column */
+  uint64_t ani_rechecked;  /* f32 values the host recomputed (rule of ani_core.hpp) */
+} gg_matrix_summary;
+
+/* rows[0..m) name rows of the sketch matrix ([n x sketch_size] u64, lens[n], as gg_pairs takes
+ * them); rows == NULL: positions 0..m-1 are rows 0..m-1 (m <= n).  Any order, a row may be listed
+ * more than once.  For positions a, b: common[a*m+b], total[a*m+b] are finch's merge counts of
+ * rows[a], rows[b] exactly as gg_ani_pairs gives them (an empty row: 0 and 0; the same row, by
+ * a == b or by a repeated index: its length twice), ani[a*m+b] = gg_ani_f32 of them, bit for bit.
+ * Each of common / total / ani may be NULL.  m <= 32768.  The host-input
+ * forms return GG_ERR_INVALID_ARG for an index >= n, lens[g] > sketch_size,
+ * m > 32768, rows == NULL with m > n, or all three outputs NULL; m == 0 is
+ * GG_OK and writes nothing.  summary may be NULL. */
+
+/* On the host (the merge itself per unordered pair, mirrored); no device, no ctx. */
+gg_status gg_ani_matrix_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                             int kmer_length, const uint32_t* rows, uint32_t m,
+                             uint32_t* common, uint32_t* total, float* ani);
+/* The same on the context's (first) device: host arrays in and out. */
+gg_status gg_ani_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                        const uint32_t* rows, uint32_t m, uint32_t* common, uint32_t* total, float* ani,
+                        gg_matrix_summary* summary);
+/* Device-resident, on the given stream; synchronises the stream.  The rows
+ * are not checked: an index >= n is never followed and is treated as an
+ * empty row; a length above the context's sketch size is read as the sketch
+ * size.  m * sketch size < 2^31. */
+gg_status gg_ani_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                               const uint32_t* d_rows, uint32_t m, uint32_t* d_common, uint32_t* d_total,
+                               float* d_ani, gg_matrix_summary* summary, void* stream);
+/* gg_sketch_files(paths, cache_dir) followed by the device form over all rows. */
+gg_status gg_ani_matrix_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, const char* cache_dir,
+                              uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);

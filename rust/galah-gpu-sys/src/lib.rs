@@ -171,6 +171,17 @@ pub struct gg_cluster_summary {
     pub reserved: u32,
 }
 
+/// What the dense ANI matrix calls report beside the matrix
+/// (`gg_matrix_summary`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gg_matrix_summary {
+    pub n_entries: u64,
+    pub n_columns: u64,
+    pub column_entries: u64,
+    pub ani_rechecked: u64,
+}
+
 /// `gg_pair_sink`: a block of compared pairs; return 0 to go on.
 pub type gg_pair_sink = Option<unsafe extern "C" fn(user: *mut c_void, pairs: *const gg_pair, n: u64) -> c_int>;
 
@@ -318,6 +329,19 @@ extern "C" {
                              offsets: *const u32, n_clusters: u32, ani: f32, cache_dir: *const c_char,
                              sum: *mut gg_validation, bad: *mut *mut gg_pair, bad_ani: *mut *mut f32,
                              n_bad: *mut u64) -> GgStatus;
+
+    // dense ANI matrix of a set of rows: common / total / f32 ANI, [m x m]
+    pub fn gg_ani_matrix_host(sketches: *const u64, lens: *const u32, n: u32, sketch_size: u32, kmer_length: c_int,
+                              rows: *const u32, m: u32, common: *mut u32, total: *mut u32, ani: *mut f32) -> GgStatus;
+    pub fn gg_ani_matrix(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, rows: *const u32, m: u32,
+                         common: *mut u32, total: *mut u32, ani: *mut f32, summary: *mut gg_matrix_summary)
+        -> GgStatus;
+    pub fn gg_ani_matrix_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32,
+                                d_rows: *const u32, m: u32, d_common: *mut u32, d_total: *mut u32, d_ani: *mut f32,
+                                summary: *mut gg_matrix_summary, stream: *mut c_void) -> GgStatus;
+    pub fn gg_ani_matrix_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, cache_dir: *const c_char,
+                               common: *mut u32, total: *mut u32, ani: *mut f32, summary: *mut gg_matrix_summary)
+        -> GgStatus;
 
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;

@@ -1,0 +1,128 @@
+"""Times the dense ANI matrix (gg_ani_matrix_device) against the
+only other way to every pair's counts and ANI on the device: the gate kernel
+at min_ani = 0 (gg_pairs_device) followed by gg_ani_f32_device.
+
+Inputs: m resident rows at sketch size s, in clusters of a given size.  A
+cluster's rows are model sketches: a base of s random 64-bit hashes, each
+member replacing a fraction of them by hashes of its own (the rows of
+different clusters share nothing).  Both paths read the same rows.  Per input:
+a warm-up call, then the median and the spread of `--calls` timed calls
+(wall clock around a synchronising call), for the matrix with all three
+outputs, the matrix with `common` alone (no ANI pass) and the baseline; the
+two paths' results are compared on a sample of pairs.  One JSON line per
+input; --out writes them to a file as well.
+
+    python scripts/ani_matrix_bench.py --m 10000 --clusters 10 1000 5000
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def model_rows(m, s, cluster, replace, seed):
+    rng = np.random.default_rng(seed)
+    sk = np.empty((m, s), np.uint64)
+    n_rep = max(1, int(s * replace))
+    for c0 in range(0, m, cluster):
+        base = rng.integers(1, 2 ** 63, s, dtype=np.uint64)
+        for g in range(c0, min(c0 + cluster, m)):
+            row = base.copy()
+            row[rng.choice(s, n_rep, replace=False)] = rng.integers(1, 2 ** 63, n_rep, dtype=np.uint64)
+            sk[g] = np.sort(row)
+    assert all(len(np.unique(r)) == s for r in sk[:: max(1, m // 50)])
+    return sk, np.full(m, s, np.uint32)
+
+
+def timed(fn, calls):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
+            "calls": calls}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--m", type=int, default=10000)
+    ap.add_argument("--sketch", type=int, default=1000)
+    ap.add_argument("--clusters", type=int, nargs="+", default=[10, 1000, 5000], help="cluster sizes, one input each")
+    ap.add_argument("--replace", type=float, default=0.05, help="fraction of a member's hashes that are its own")
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import torch
+
+    os.environ["GALAHGPU_PAIRS_KERNEL"] = "gate"  # the baseline is the gate kernel, whatever "auto" would take
+    import galah_amd as ga
+
+    m, s = a.m, a.sketch
+    lines = []
+    with ga.Context(k=21, sketch_size=s, seed=0, device=0) as ctx:
+        for cluster in a.clusters:
+            sk, lens = model_rows(m, s, cluster, a.replace, seed=cluster)
+            d_sk = torch.from_numpy(sk.view(np.int64)).cuda()
+            d_lens = torch.from_numpy(lens.view(np.int32)).cuda()
+            d_common = torch.zeros((m, m), dtype=torch.int32, device="cuda")
+            d_total = torch.zeros((m, m), dtype=torch.int32, device="cuda")
+            d_ani = torch.zeros((m, m), dtype=torch.float32, device="cuda")
+            summary = {}
+
+            def matrix_all():
+                summary.update(ctx.ani_matrix_device(d_sk, d_lens, m, None, m, d_common, d_total, d_ani))
+
+            def matrix_common():
+                ctx.ani_matrix_device(d_sk, d_lens, m, None, m, d_common, None, None)
+
+            res = {"input": "m=%d s=%d clusters of %d" % (m, s, cluster), "matrix_all": timed(matrix_all, a.calls),
+                   "matrix_common_only": timed(matrix_common, a.calls), "summary": dict(summary)}
+            if not a.no_baseline:
+                n_pairs = m * (m - 1) // 2
+                d_pairs = torch.zeros((n_pairs, 4), dtype=torch.int32, device="cuda")
+                d_count = torch.zeros(1, dtype=torch.int64, device="cuda")
+                d_pani = torch.zeros(n_pairs, dtype=torch.float32, device="cuda")
+
+                def baseline():
+                    d_count.zero_()
+                    ctx.pairs_device(d_sk, d_lens, m, 0, ga.pair_tiles(m), 0.0, d_pairs, n_pairs, d_count)
+                    torch.cuda.synchronize()
+                    ctx.ani_f32_device(d_pairs, int(d_count.item()), d_pani)
+
+                res["pairs_gate_then_ani_f32"] = timed(baseline, a.calls)
+                assert int(d_count.item()) == n_pairs
+                # the same answers: a sample of the pair list against the matrix
+                idx = torch.randint(0, n_pairs, (100000,), device="cuda")
+                p = d_pairs[idx].long()
+                i, j = p[:, 0] & 0xFFFFFFFF, p[:, 1] & 0xFFFFFFFF
+                assert torch.equal(d_common[i, j].long(), p[:, 2]) and torch.equal(d_total[i, j].long(), p[:, 3])
+                assert torch.equal(d_ani[i, j].view(torch.int32), d_pani[idx].view(torch.int32))
+                res["sample_equal"] = True
+                res["speedup_all"] = round(res["pairs_gate_then_ani_f32"]["median_ms"] / res["matrix_all"]["median_ms"], 2)
+                del d_pairs, d_pani
+            print(json.dumps(res), flush=True)
+            lines.append(res)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
