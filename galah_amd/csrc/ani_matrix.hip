@@ -37,6 +37,10 @@
 // No workgroup waits for another, the kernels are not persistent, and the
 // only atomic is the flagged list's counter (ani_flag.hpp).  The kernels are
 // launched plainly (no gg_timing_read slot).
+//
+// The matrices of many groups in one call are further down:
+// the same product kernel instantiated on MxGroupLaunch, fed by entries sorted
+// by (group, hash) with column ids local to a group.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -178,6 +182,15 @@ struct MxLaunch {
   AniFlagged* list;
   uint64_t cap;
   unsigned long long* count;
+  static constexpr bool kGroups = false;
+};
+// the grouped form (matrix_core.hpp, groups): m is not read, a workgroup finds its group in tp_off
+struct MxGroupLaunch : MxLaunch {
+  const uint32_t* offsets;   // [n_groups + 1] first position of a group
+  const uint32_t* tp_off;    // [n_groups + 1] first workgroup of a group
+  const uint64_t* cell_off;  // [n_groups + 1] first cell of a group's block
+  uint32_t n_groups;
+  static constexpr bool kGroups = true;
 };
 
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
@@ -185,25 +198,40 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
   return v;
 }
 
-__global__ __launch_bounds__(256) void mx_common_kernel(MxLaunch a) {
+// L = MxLaunch: the tile pairs of one [m x m] matrix.  L = MxGroupLaunch: the
+// tile pairs of every group in turn; positions, bounds and cells are the
+// group's (first position p0, m positions, first cell c0), the pieces hold
+// group-local ids, and a flagged cell is listed on both sides of the diagonal
+// (the list's patch then needs no matrix width).
+template <class L>
+__global__ __launch_bounds__(256) void mx_common_kernel(L a) {
   __shared__ __align__(16) uint8_t image[2 * kTileBytes];
   __shared__ uint64_t s_last[2 * kTile];
   __shared__ uint32_t s_row[2 * kTile], s_len[2 * kTile], s_cnt[2 * kTile], s_cur[2 * kTile];
   __shared__ uint32_t s_min[2];
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  uint32_t ti, tj;
-  matrix::tile_pair_of(blockIdx.x, &ti, &tj);
+  uint32_t ti, tj, p0 = 0, m = a.m;
+  uint64_t c0 = 0;
+  if constexpr (L::kGroups) {
+    const uint32_t g = matrix::group_of_workgroup(a.tp_off, a.n_groups, blockIdx.x);
+    p0 = a.offsets[g];
+    m = a.offsets[g + 1] - p0;
+    c0 = a.cell_off[g];
+    matrix::tile_pair_of(blockIdx.x - a.tp_off[g], &ti, &tj);
+  } else {
+    matrix::tile_pair_of(blockIdx.x, &ti, &tj);
+  }
   const bool diag = ti == tj;
   const uint32_t sides = diag ? 1u : 2u;
   // rows 0 .. 63 of the state are tile ti's positions, 64 .. 127 tile tj's (not filled for a diagonal tile)
   if (t < sides * kTile) {
     const uint32_t pos = (t < kTile ? ti : tj) * kTile + (t & (kTile - 1));
-    const bool ok = pos < a.m;
-    const uint32_t row = ok ? a.pos_row[pos] : kNoRow;
-    const uint32_t len = ok ? a.pos_len[pos] : 0u;
+    const bool ok = pos < m;
+    const uint32_t row = ok ? a.pos_row[p0 + pos] : kNoRow;
+    const uint32_t len = ok ? a.pos_len[p0 + pos] : 0u;
     s_row[t] = row;
     s_len[t] = len;
-    s_cnt[t] = ok ? a.piece_cnt[pos] : 0u;
+    s_cnt[t] = ok ? a.piece_cnt[p0 + pos] : 0u;
     s_cur[t] = 0;
     s_last[t] = len ? a.sk[(uint64_t)row * a.s + len - 1] : 0ull;
   }
@@ -220,7 +248,7 @@ __global__ __launch_bounds__(256) void mx_common_kernel(MxLaunch a) {
       if (t < sides * kTile) {
         const uint32_t pos = (t < kTile ? ti : tj) * kTile + (t & (kTile - 1));
         const uint32_t cnt = s_cnt[t];
-        const uint32_t* pc = a.piece + (uint64_t)pos * a.s;  // (not read when cnt == 0)
+        const uint32_t* pc = a.piece + (uint64_t)(p0 + pos) * a.s;  // (not read when cnt == 0)
         const uint32_t cur = matrix::cursor_at(pc, s_cur[t], cnt, k0);
         s_cur[t] = cur;
         if (cur < cnt) next = pc[cur];
@@ -241,7 +269,7 @@ __global__ __launch_bounds__(256) void mx_common_kernel(MxLaunch a) {
     for (uint32_t r = wave; r < sides * kTile; r += 4) {
       const uint32_t pos = (r < kTile ? ti : tj) * kTile + (r & (kTile - 1));
       const uint32_t cnt = s_cnt[r];
-      const uint32_t* pc = a.piece + (uint64_t)pos * a.s;
+      const uint32_t* pc = a.piece + (uint64_t)(p0 + pos) * a.s;
       uint8_t* img = image + (r < kTile ? 0u : kTileBytes);
       for (uint32_t e = s_cur[r] + lane;; e += 64) {  // (s_cur[r], cnt are the wave's)
         bool in = e < cnt;
@@ -276,15 +304,17 @@ __global__ __launch_bounds__(256) void mx_common_kernel(MxLaunch a) {
     for (uint32_t reg = 0; reg < 4; ++reg) {
       const uint32_t ra = wave * 16 + matrix::cd_row(lane, reg), rb = nb * 16 + matrix::cd_col(lane);
       const uint32_t pa = ti * kTile + ra, pb = tj * kTile + rb;
-      const bool live = pa < a.m && pb < a.m && (!diag || pa <= pb);
+      const bool live = pa < m && pb < m && (!diag || pa <= pb);
       uint32_t common = 0, total = 0;
+      uint64_t ab = 0, ba = 0;
       bool flagged = false;
       if (live) {
         const uint32_t ga = s_row[ra], gb = s_row[sb + rb];
         matrix::cell_counts(pa == pb || ga == gb, a.sk + (uint64_t)ga * a.s, s_len[ra], s_last[ra],
                             a.sk + (uint64_t)gb * a.s, s_len[sb + rb], s_last[sb + rb], (uint32_t)acc[nb][reg], &common,
                             &total);
-        const uint64_t ab = (uint64_t)pa * a.m + pb, ba = (uint64_t)pb * a.m + pa;
+        ab = c0 + (uint64_t)pa * m + pb;
+        ba = c0 + (uint64_t)pb * m + pa;
         if (a.common) {
           a.common[ab] = common;
           a.common[ba] = common;
@@ -301,7 +331,14 @@ __global__ __launch_bounds__(256) void mx_common_kernel(MxLaunch a) {
         }
       }
       // (a * m + b < 2^30; a flagged cell is off the diagonal, a < b or of an off-diagonal tile)
-      if (a.ani) ani_flag_push(flagged, pa * a.m + pb, common, total, a.list, a.cap, a.count);
+      if constexpr (L::kGroups) {  // (a cell index is < 2^32: group_limits_ok)
+        if (a.ani) {
+          ani_flag_push(flagged, (uint32_t)ab, common, total, a.list, a.cap, a.count);
+          ani_flag_push(flagged, (uint32_t)ba, common, total, a.list, a.cap, a.count);
+        }
+      } else {
+        if (a.ani) ani_flag_push(flagged, pa * a.m + pb, common, total, a.list, a.cap, a.count);
+      }
     }
   }
 }
@@ -376,13 +413,13 @@ gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_l
           a.list = list;
           a.cap = cap;
           a.count = count;
-          hipLaunchKernelGGL(mx_common_kernel, grid, dim3(256), 0, st, a);
+          hipLaunchKernelGGL(mx_common_kernel<MxLaunch>, grid, dim3(256), 0, st, a);
           return hipGetLastError();
         },
         d_ani, nullptr, m, &flagged, st);
     if (r != GG_OK) return r;
   } else {
-    hipLaunchKernelGGL(mx_common_kernel, grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mx_common_kernel<MxLaunch>, grid, dim3(256), 0, st, a);
     GG_HIP(c, hipGetLastError());
     GG_HIP(c, hipStreamSynchronize(st));
   }
@@ -391,6 +428,304 @@ gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_l
     sum->n_columns = n_columns;
     sum->column_entries = column_entries;
     sum->ani_rechecked = 2 * flagged;  // cells: the matrix mirrors each listed entry
+  }
+  return GG_OK;
+}
+
+// ---- the matrices of many groups in one call ----------------
+//   mxg_positions_kernel  every position's group (a search of offsets), row
+//                         and length, for any number of positions;
+//   hipcub ExclusiveSum   the positions' first entries; mxg_segments_kernel
+//                         every group's first entry;
+//   mx_keys_kernel        as above, over all P positions;
+//   the sort by (group, hash): the 64-bit sort above, then a stable sort of
+//                         (group, slot) on the group's bits and a gather of
+//                         the hashes; one group needs the first only
+//                         (a segmented sort over the groups' entry ranges was
+//                         measured and dropped);
+//   mxg_entry_groups_kernel, mxg_flags_kernel, InclusiveSum, mxg_ids_kernel:
+//                         the grouped column rule, ids local to the group;
+//   mx_pieces_kernel      unchanged;
+//   mxg_single_kernel     the one cell of every group of one position;
+//   mx_common_kernel<MxGroupLaunch>  the groups of two positions or more.
+namespace {
+
+__global__ __launch_bounds__(256) void mxg_positions_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
+                                                            const uint32_t* __restrict__ members,
+                                                            const uint32_t* __restrict__ offsets, uint32_t n_groups,
+                                                            uint32_t P, uint32_t* __restrict__ pos_row,
+                                                            uint32_t* __restrict__ pos_len,
+                                                            uint32_t* __restrict__ pos_grp) {
+  for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p <= P; p += gridDim.x * 256) {
+    if (p == P) {  // (the scan's last item: its exclusive sum is the number of entries)
+      pos_len[p] = 0;
+      continue;
+    }
+    const uint32_t g = members[p];
+    const bool ok = g < n;
+    pos_row[p] = ok ? g : kNoRow;
+    pos_len[p] = ok ? min(lens[g], s) : 0u;
+    pos_grp[p] = matrix::group_of_position(offsets, n_groups, p);
+  }
+}
+
+// seg[g] the first sorted entry of group g, seg[n_groups] the number of entries
+__global__ __launch_bounds__(256) void mxg_segments_kernel(const uint32_t* __restrict__ offsets, uint32_t n_groups,
+                                                           const uint32_t* __restrict__ pos_off,
+                                                           uint32_t* __restrict__ seg) {
+  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g <= n_groups; g += gridDim.x * 256) seg[g] = pos_off[offsets[g]];
+}
+
+// the group of every hash-sorted entry from its slot (the padding: n_groups, behind every group)
+__global__ __launch_bounds__(256) void mxg_entry_groups_kernel(const uint32_t* __restrict__ slot_of, uint32_t N,
+                                                               uint32_t s, const uint32_t* __restrict__ pos_grp,
+                                                               uint32_t n_groups, uint32_t* __restrict__ grp) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+    const uint32_t slot = slot_of[i];
+    grp[i] = slot == kNoColumn ? n_groups : pos_grp[slot / s];
+  }
+}
+
+// the hash of every entry from its slot, after the stable sort on the group
+__global__ __launch_bounds__(256) void mxg_gather_kernel(const uint64_t* __restrict__ sk, uint32_t s,
+                                                         const uint32_t* __restrict__ pos_row,
+                                                         const uint32_t* __restrict__ slot_of,
+                                                         const uint32_t* __restrict__ pos_off, uint32_t P,
+                                                         uint64_t* __restrict__ K) {
+  const uint32_t ne = pos_off[P];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256) {
+    const uint32_t slot = slot_of[i], p = slot / s;
+    K[i] = sk[(uint64_t)pos_row[p] * s + (slot - p * s)];
+  }
+}
+
+__global__ __launch_bounds__(256) void mxg_flags_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ grp,
+                                                        uint32_t N, const uint32_t* __restrict__ pos_off, uint32_t P,
+                                                        uint64_t* __restrict__ flags) {
+  const uint32_t ne = pos_off[P];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
+    flags[i] = i < ne ? matrix::column_flags(K, grp, i, ne) : 0ull;
+}
+
+__global__ __launch_bounds__(256) void mxg_ids_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ grp,
+                                                      const uint32_t* __restrict__ slot_of,
+                                                      const uint64_t* __restrict__ sums,
+                                                      const uint32_t* __restrict__ seg,
+                                                      const uint32_t* __restrict__ pos_off, uint32_t P,
+                                                      uint32_t* __restrict__ id_of) {
+  const uint32_t ne = pos_off[P];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256)
+    id_of[slot_of[i]] = matrix::in_column(K, grp, i, ne)
+                            ? matrix::column_id(sums[i]) - matrix::group_first_id(sums, seg[grp[i]])
+                            : kNoColumn;
+}
+
+// a group of one position: its cell is the diagonal rule's
+__global__ __launch_bounds__(256) void mxg_single_kernel(const uint32_t* __restrict__ offsets,
+                                                         const uint64_t* __restrict__ cell_off, uint32_t n_groups,
+                                                         const uint32_t* __restrict__ pos_len,
+                                                         uint32_t* __restrict__ common, uint32_t* __restrict__ total,
+                                                         float* __restrict__ ani) {
+  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n_groups; g += gridDim.x * 256) {
+    const uint32_t p = offsets[g];
+    if (offsets[g + 1] - p != 1) continue;
+    const uint32_t len = pos_len[p];
+    const uint64_t cell = cell_off[g];
+    if (common) common[cell] = len;
+    if (total) total[cell] = len;
+    if (ani) ani[cell] = len ? 1.0f : 0.0f;
+  }
+}
+
+// offsets of a grouped call (host words in every form): they begin at 0,
+// ascend and keep the limits; cell_off / tp_off (may be null) receive the layout
+gg_status check_group_offsets(const std::string& w, const uint32_t* offsets, uint32_t n_groups, uint64_t sketch_size,
+                              uint64_t* cell_off, uint32_t* tp_off, std::string& err) {
+  if (!offsets) {
+    err = w + ": null argument";
+    return GG_ERR_INVALID_ARG;
+  }
+  if (offsets[0] != 0) {
+    err = w + ": offsets[0] is not 0";
+    return GG_ERR_INVALID_ARG;
+  }
+  for (uint32_t g = 0; g < n_groups; ++g)
+    if (offsets[g + 1] < offsets[g]) {
+      err = w + ": offsets do not ascend";
+      return GG_ERR_INVALID_ARG;
+    }
+  if (!matrix::group_layout(offsets, n_groups, sketch_size, cell_off, tp_off)) {
+    err = w + ": 2^31 sketch slots, 2^32 cells or 2^31 tile pairs, or more";
+    return GG_ERR_INVALID_ARG;
+  }
+  return GG_OK;
+}
+
+uint32_t bits_for(uint32_t values) {  // the bits that hold 0 .. values - 1
+  uint32_t b = 1;
+  while (b < 32 && (1ull << b) < values) ++b;
+  return b;
+}
+
+}  // namespace
+
+gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                                   const uint32_t* d_members, const uint32_t* offsets, uint32_t n_groups,
+                                   uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
+                                   hipStream_t st) {
+  const char* who = "gg_ani_matrix_groups";
+  if (sum) *sum = gg_matrix_summary{};
+  if (n_groups == 0) return GG_OK;
+  const uint32_t s = c->s, G = n_groups;
+  // the layout on the host: offsets arrive from it, and it shapes the launches
+  uint32_t *h_off, *h_tp;
+  uint64_t* h_cell;
+  GG_HIP(c, host_scratch_t(c, "mxg_h_off", (size_t)2 * (G + 1), &h_off));
+  GG_HIP(c, host_scratch_t(c, "mxg_h_cell", (size_t)G + 1, &h_cell));
+  h_tp = h_off + (G + 1);
+  std::string err;
+  const gg_status chk = check_group_offsets(who, offsets, G, s, h_cell, h_tp, err);
+  if (chk != GG_OK) return fail(c, chk, err);
+  const uint32_t P = offsets[G];
+  if (P == 0) return GG_OK;
+  memcpy(h_off, offsets, (size_t)(G + 1) * sizeof(uint32_t));
+  const uint32_t N = P * s, tile_pairs = h_tp[G];
+  const uint64_t cells = h_cell[G];
+  bool singles = false;
+  for (uint32_t g = 0; g < G && !singles; ++g) singles = offsets[g + 1] - offsets[g] == 1;
+
+  uint32_t *pos_row, *pos_len, *pos_grp, *pos_off, *piece_cnt, *d_off, *d_tp, *seg, *vals_in, *vals_out, *grp_in, *grp_out,
+      *piece;
+  uint64_t *d_cell, *keys_in, *keys_out, *sums, *h_back;
+  GG_HIP(c, scratch_t(c, "mxg_pos", (size_t)5 * (P + 1), &pos_row));
+  pos_len = pos_row + (P + 1);
+  pos_grp = pos_len + (P + 1);
+  pos_off = pos_grp + (P + 1);
+  piece_cnt = pos_off + (P + 1);
+  GG_HIP(c, scratch_t(c, "mxg_off", (size_t)3 * (G + 1), &d_off));
+  d_tp = d_off + (G + 1);
+  seg = d_tp + (G + 1);
+  GG_HIP(c, scratch_t(c, "mxg_cell", (size_t)G + 1, &d_cell));
+  GG_HIP(c, scratch_t(c, "mx_keys_in", (size_t)N, &keys_in));
+  GG_HIP(c, scratch_t(c, "mx_keys_out", (size_t)N, &keys_out));
+  GG_HIP(c, scratch_t(c, "mx_sums", (size_t)N, &sums));
+  GG_HIP(c, scratch_t(c, "mx_vals_in", (size_t)N, &vals_in));
+  GG_HIP(c, scratch_t(c, "mx_vals_out", (size_t)N, &vals_out));
+  GG_HIP(c, scratch_t(c, "mxg_grp_in", (size_t)N, &grp_in));
+  GG_HIP(c, scratch_t(c, "mxg_grp_out", (size_t)N, &grp_out));
+  GG_HIP(c, scratch_t(c, "mx_piece", (size_t)N, &piece));
+  GG_HIP(c, host_scratch_t(c, "mx_back", 2, &h_back));
+  const int group_bits = (int)bits_for(G + 1);
+  size_t sort_bytes = 0, sort2_bytes = 0, scan_bytes = 0, off_bytes = 0;
+  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, 64));
+  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort2_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, group_bits));
+  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N));
+  GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, off_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                             (int)(P + 1)));
+  const size_t tmp_bytes = std::max(std::max(sort_bytes, sort2_bytes), std::max(scan_bytes, off_bytes));
+  uint8_t* tmp;
+  GG_HIP(c, scratch_t(c, "mx_tmp", std::max<size_t>(tmp_bytes, 1), &tmp));
+
+  GG_HIP(c, hipMemcpyAsync(d_off, h_off, (size_t)2 * (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  GG_HIP(c, hipMemcpyAsync(d_cell, h_cell, (size_t)(G + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(mxg_positions_kernel, grid_for((uint64_t)P + 1), dim3(256), 0, st, d_lens, n, s, d_members, d_off, G,
+                     P, pos_row, pos_len, pos_grp);
+  GG_HIP(c, hipGetLastError());
+  size_t bytes = tmp_bytes;
+  GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)pos_len, pos_off, (int)(P + 1), st));
+  hipLaunchKernelGGL(mxg_segments_kernel, grid_for((uint64_t)G + 1), dim3(256), 0, st, d_off, G, pos_off, seg);
+  GG_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(mx_keys_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, P, pos_row, pos_len, pos_off, keys_in,
+                     vals_in);
+  GG_HIP(c, hipGetLastError());
+  // K, slot_of, grp: the entries sorted by (group, hash); everything from the number of entries on is padding
+  uint64_t* K = keys_out;
+  uint32_t *slot_of = vals_out, *grp = grp_out;
+  bytes = tmp_bytes;
+  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
+                                               vals_out, (int)N, 0, 64, st));
+  if (G > 1) {
+    hipLaunchKernelGGL(mxg_entry_groups_kernel, grid_for(N), dim3(256), 0, st, vals_out, N, s, pos_grp, G, grp_in);
+    GG_HIP(c, hipGetLastError());
+    bytes = tmp_bytes;
+    GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint32_t*)grp_in, grp_out, (const uint32_t*)vals_out,
+                                                 vals_in, (int)N, 0, group_bits, st));
+    slot_of = vals_in;
+    K = keys_in;
+    hipLaunchKernelGGL(mxg_gather_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, pos_row, slot_of, pos_off, P, K);
+    GG_HIP(c, hipGetLastError());
+  } else {
+    GG_HIP(c, hipMemsetAsync(grp, 0, (size_t)N * sizeof(uint32_t), st));
+  }
+  uint64_t* flags = K == keys_out ? keys_in : keys_out;  // (the buffer the sorted keys are not in)
+  uint32_t* id_of = slot_of == vals_out ? vals_in : vals_out;
+  hipLaunchKernelGGL(mxg_flags_kernel, grid_for(N), dim3(256), 0, st, K, grp, N, pos_off, P, flags);
+  GG_HIP(c, hipGetLastError());
+  bytes = tmp_bytes;
+  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
+  hipLaunchKernelGGL(mxg_ids_kernel, grid_for(N), dim3(256), 0, st, K, grp, slot_of, sums, seg, pos_off, P, id_of);
+  GG_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(mx_pieces_kernel, dim3(P), dim3(256), 0, st, id_of, pos_len, s, piece, piece_cnt);
+  GG_HIP(c, hipGetLastError());
+  // entries, columns, column entries: the one read-back before the product
+  // (the tile pairs' total is the host's: offsets came from it)
+  GG_HIP(c, hipMemcpyAsync(&h_back[0], sums + (N - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  GG_HIP(c, hipMemcpyAsync(&h_back[1], pos_off + P, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  GG_HIP(c, hipStreamSynchronize(st));
+  const uint64_t n_columns = (uint32_t)h_back[0], column_entries = h_back[0] >> 32, n_entries = (uint32_t)h_back[1];
+  if (n_entries > N || column_entries > n_entries || 2 * n_columns > column_entries)
+    return fail(c, GG_ERR_INTERNAL, std::string(who) + ": bad column counts");
+
+  if (singles) {
+    hipLaunchKernelGGL(mxg_single_kernel, grid_for(G), dim3(256), 0, st, d_off, d_cell, G, pos_len, d_common, d_total,
+                       d_ani);
+    GG_HIP(c, hipGetLastError());
+  }
+  MxGroupLaunch a{};
+  a.sk = d_sk;
+  a.s = s;
+  a.m = 0;
+  a.pos_row = pos_row;
+  a.pos_len = pos_len;
+  a.piece = piece;
+  a.piece_cnt = piece_cnt;
+  a.common = d_common;
+  a.total = d_total;
+  a.ani = d_ani;
+  a.k = c->k;
+  a.offsets = d_off;
+  a.tp_off = d_tp;
+  a.cell_off = d_cell;
+  a.n_groups = G;
+  const dim3 grid(tile_pairs);
+  uint64_t flagged = 0;
+  if (tile_pairs && d_ani) {
+    const gg_status r = ani_flagged_passes(
+        c, who, cells,
+        [&](double E, AniFlagged* list, uint64_t cap, unsigned long long* count) {
+          a.E = E;
+          a.list = list;
+          a.cap = cap;
+          a.count = count;
+          hipLaunchKernelGGL(mx_common_kernel<MxGroupLaunch>, grid, dim3(256), 0, st, a);
+          return hipGetLastError();
+        },
+        d_ani, nullptr, 0, &flagged, st);
+    if (r != GG_OK) return r;
+  } else {
+    if (tile_pairs) {
+      hipLaunchKernelGGL(mx_common_kernel<MxGroupLaunch>, grid, dim3(256), 0, st, a);
+      GG_HIP(c, hipGetLastError());
+    }
+    GG_HIP(c, hipStreamSynchronize(st));
+  }
+  if (sum) {
+    sum->n_entries = n_entries;
+    sum->n_columns = n_columns;
+    sum->column_entries = column_entries;
+    sum->ani_rechecked = flagged;  // cells: both sides of the diagonal are listed
   }
   return GG_OK;
 }
@@ -459,6 +794,74 @@ gg_status ani_matrix_ctx(gg_ctx* pm, const uint64_t* sketches, const uint32_t* l
   if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", cells, &d_total));
   if (ani) GG_HIP(pm, scratch_t(pm, "mx_h_ani", cells, &d_ani));
   const gg_status st = ani_matrix_device(pm, d_sk, d_len, n, d_rows, m, d_common, d_total, d_ani, summary, pm->stream);
+  if (st != GG_OK) return st;
+  if (common) GG_HIP(pm, hipMemcpyAsync(common, d_common, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  if (total) GG_HIP(pm, hipMemcpyAsync(total, d_total, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  if (ani) GG_HIP(pm, hipMemcpyAsync(ani, d_ani, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  GG_HIP(pm, hipStreamSynchronize(pm->stream));
+  return GG_OK;
+}
+
+// the checks of the grouped host-input forms: check_matrix_input's, applied to members and offsets
+gg_status check_groups_input(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                             uint32_t sketch_size, int k, const uint32_t* members, const uint32_t* offsets,
+                             uint32_t n_groups, const void* common, const void* total, const void* ani,
+                             std::string& err) {
+  if (k < 1 || k > 32 || sketch_size < 1) {
+    err = w + ": kmer_length must be 1..32 and sketch_size at least 1";
+    return GG_ERR_INVALID_ARG;
+  }
+  const gg_status st = check_group_offsets(w, offsets, n_groups, sketch_size, nullptr, nullptr, err);
+  if (st != GG_OK) return st;
+  const uint32_t P = offsets[n_groups];
+  if (P == 0) return GG_OK;
+  if (!common && !total && !ani) {
+    err = w + ": no output asked for";
+    return GG_ERR_INVALID_ARG;
+  }
+  if (!members || (n && (!sketches || !lens))) {
+    err = w + ": null argument";
+    return GG_ERR_INVALID_ARG;
+  }
+  for (uint32_t g = 0; g < n; ++g)
+    if (lens[g] > sketch_size) {
+      err = w + ": sketch longer than sketch_size";
+      return GG_ERR_INVALID_ARG;
+    }
+  for (uint32_t p = 0; p < P; ++p)
+    if (members[p] >= n) {
+      err = w + ": row index out of range";
+      return GG_ERR_INVALID_ARG;
+    }
+  return GG_OK;
+}
+
+gg_status ani_matrix_groups_ctx(gg_ctx* pm, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                                const uint32_t* members, const uint32_t* offsets, uint32_t n_groups, uint32_t* common,
+                                uint32_t* total, float* ani, gg_matrix_summary* summary) {
+  std::string err;
+  const gg_status chk = check_groups_input("gg_ani_matrix_groups", sketches, lens, n, pm->s, pm->k, members, offsets,
+                                           n_groups, common, total, ani, err);
+  if (chk != GG_OK) return fail(pm, chk, err);
+  const uint32_t P = offsets[n_groups];
+  if (P == 0) return GG_OK;
+  if (hipSetDevice(pm->device) != hipSuccess) return fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  uint64_t cells = 0;
+  for (uint32_t g = 0; g < n_groups; ++g) cells += (uint64_t)(offsets[g + 1] - offsets[g]) * (offsets[g + 1] - offsets[g]);
+  uint64_t* d_sk = nullptr;
+  uint32_t *d_len = nullptr, *d_members = nullptr, *d_common = nullptr, *d_total = nullptr;
+  float* d_ani = nullptr;
+  GG_HIP(pm, scratch_t(pm, "mx_h_sk", (size_t)n * pm->s, &d_sk));
+  GG_HIP(pm, scratch_t(pm, "mx_h_len", (size_t)n, &d_len));
+  GG_HIP(pm, scratch_t(pm, "mx_h_rows", (size_t)P, &d_members));
+  GG_HIP(pm, hipMemcpyAsync(d_sk, sketches, (size_t)n * pm->s * sizeof(uint64_t), hipMemcpyHostToDevice, pm->stream));
+  GG_HIP(pm, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
+  GG_HIP(pm, hipMemcpyAsync(d_members, members, (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
+  if (common) GG_HIP(pm, scratch_t(pm, "mx_h_common", (size_t)cells, &d_common));
+  if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", (size_t)cells, &d_total));
+  if (ani) GG_HIP(pm, scratch_t(pm, "mx_h_ani", (size_t)cells, &d_ani));
+  const gg_status st = ani_matrix_groups_device(pm, d_sk, d_len, n, d_members, offsets, n_groups, d_common, d_total,
+                                                d_ani, summary, pm->stream);
   if (st != GG_OK) return st;
   if (common) GG_HIP(pm, hipMemcpyAsync(common, d_common, cells * 4, hipMemcpyDeviceToHost, pm->stream));
   if (total) GG_HIP(pm, hipMemcpyAsync(total, d_total, cells * 4, hipMemcpyDeviceToHost, pm->stream));
@@ -552,6 +955,91 @@ gg_status gg_ani_matrix_files(gg_ctx* ctx, const char* const* paths, uint32_t n_
   const gg_status st = gg_sketch_files(ctx, paths, n_paths, cache_dir, sk.data(), lens.data(), nullptr);
   if (st != GG_OK) return st;
   return gg_ani_matrix(ctx, sk.data(), lens.data(), n_paths, nullptr, n_paths, common, total, ani, summary);
+}
+
+gg_status gg_ani_matrix_group_cells(const uint32_t* offsets, uint32_t n_groups, uint64_t* cell_offsets) {
+  std::string err;
+  gg_status st = GG_OK;
+  if (!cell_offsets) {
+    err = "gg_ani_matrix_group_cells: null argument";
+    st = GG_ERR_INVALID_ARG;
+  } else {
+    st = check_group_offsets("gg_ani_matrix_group_cells", offsets, n_groups, 1, cell_offsets, nullptr, err);
+  }
+  if (st != GG_OK) set_thread_error(err);
+  return st;
+}
+
+gg_status gg_ani_matrix_groups_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                                    int kmer_length, const uint32_t* members, const uint32_t* offsets,
+                                    uint32_t n_groups, uint32_t* common, uint32_t* total, float* ani) {
+  std::string err;
+  const gg_status st = check_groups_input("gg_ani_matrix_groups_host", sketches, lens, n, sketch_size, kmer_length,
+                                          members, offsets, n_groups, common, total, ani, err);
+  if (st != GG_OK) {
+    set_thread_error(err);
+    return st;
+  }
+  // every group on its own: the merge itself per unordered pair, mirrored
+  size_t cell0 = 0;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    const uint32_t* rows = members + offsets[g];
+    const size_t m = offsets[g + 1] - offsets[g];
+    for (size_t a = 0; a < m; ++a)
+      for (size_t b = a; b < m; ++b) {
+        uint32_t c, t;
+        validate::merge_counts(sketches + (size_t)rows[a] * sketch_size, lens[rows[a]],
+                               sketches + (size_t)rows[b] * sketch_size, lens[rows[b]], &c, &t);
+        const size_t ab = cell0 + a * m + b, ba = cell0 + b * m + a;
+        if (common) common[ab] = common[ba] = c;
+        if (total) total[ab] = total[ba] = t;
+        if (ani) ani[ab] = ani[ba] = (float)ani_f64(c, t, kmer_length);
+      }
+    cell0 += m * m;
+  }
+  return GG_OK;
+}
+
+gg_status gg_ani_matrix_groups(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                               const uint32_t* members, const uint32_t* offsets, uint32_t n_groups, uint32_t* common,
+                               uint32_t* total, float* ani, gg_matrix_summary* summary) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  gg_ctx* pm = primary(ctx);
+  if (summary) *summary = gg_matrix_summary{};
+  const gg_status st = ani_matrix_groups_ctx(pm, sketches, lens, n, members, offsets, n_groups, common, total, ani,
+                                             summary);
+  if (st != GG_OK) {
+    if (summary) *summary = gg_matrix_summary{};
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
+}
+
+gg_status gg_ani_matrix_groups_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                      const uint32_t* d_members, const uint32_t* offsets, uint32_t n_groups,
+                                      uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* summary,
+                                      void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  gg_ctx* pm = primary(ctx);
+  gg_status st = GG_OK;
+  if (summary) *summary = gg_matrix_summary{};
+  const uint32_t P = n_groups && offsets ? offsets[n_groups] : 0;
+  if (n_groups && !offsets)
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_groups_device: null offsets");
+  else if (P && !d_common && !d_total && !d_ani)
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_groups_device: no output asked for");
+  else if (P && (!d_members || (n && (!d_sketches || !d_lens))))
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_groups_device: null buffer");
+  else if (hipSetDevice(pm->device) != hipSuccess)
+    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  else
+    st = ani_matrix_groups_device(pm, d_sketches, d_lens, n, d_members, offsets, n_groups, d_common, d_total, d_ani,
+                                  summary, (hipStream_t)stream);
+  if (st != GG_OK) {
+    if (summary) *summary = gg_matrix_summary{};
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
 }
 
 }  // extern "C"

@@ -278,6 +278,20 @@ gg_status ani_flagged_passes(gg_ctx* c, const char* who, uint64_t n_items, const
 gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
                             uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
                             hipStream_t st);
+// The dense matrices of many groups in one call (ani_matrix.hip, by
+// matrix_core.hpp, groups): group g is d_members[offsets[g] .. offsets[g+1])
+// (offsets: host words), its [m_g x m_g] block begins at the sum of the
+// earlier groups' m^2.  Each output may be null.  Synchronises st.
+gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                                   const uint32_t* d_members, const uint32_t* offsets, uint32_t n_groups,
+                                   uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
+                                   hipStream_t st);
+// K2 over every tile of n resident rows into context scratch (resident.cpp):
+// max(2^20, 16 n) pairs clipped to n (n - 1) / 2, the count read back, one
+// retry at the exact count.  *d_out the pairs (unsorted), *cnt their number,
+// *passes 1 or 2 (n < 2: nothing is run, 0 pairs).  Synchronises st.
+gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                            float min_ani, gg_pair** d_out, uint64_t* cnt, uint32_t* passes, hipStream_t st);
 // Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
 // ani_f32_device, cluster_device; with sum, the partition of
 // preclusters_device.  *d_pairs / *d_ani (may be null) receive the scratch

@@ -170,5 +170,137 @@ inline Columns columns_host(const uint64_t* sketches, const uint32_t* lens, uint
   return c;
 }
 
+// ---- groups ------------------------------------------------------
+// The matrices of many groups in one call.  Group g is members[offsets[g] ..
+// offsets[g + 1]): row indices in any order, a row may be listed twice in a
+// group and in several groups, a group may be empty.  Positions are numbered
+// through all groups (P = offsets[n_groups]); tiles of kTile positions are
+// local to a group, the first tile of group g begins at offsets[g].
+//   The grouped column rule.  A column of group g is a distinct hash held at
+//     two or more positions *of g*: the same hash in two groups gives two
+//     columns (or none, held once in each).  The entries are sorted by
+//     (group, hash), Gr[i] the group of entry i; column ids ascend with
+//     (group, hash), and a piece stores ids local to its group (the id minus
+//     the group's first id), so that cursor_at, next_chunk and the chunk loop
+//     see one group's columns numbered from 0.
+//   Cells.  A cell exists only inside a group: block g begins at cell_off[g] =
+//     sum over h < g of m_h^2 and is row-major [m_g x m_g]; the diagonal rule,
+//     the off-diagonal rule and cell_counts are unchanged.
+//   Workgroups.  Group g takes group_tile_pairs(m_g) workgroups, none when
+//     m_g < 2 (the one cell of a single position is (len, len) without a
+//     product); tp_off is their exclusive sum and workgroup w belongs to the
+//     group g with tp_off[g] <= w < tp_off[g + 1].
+GG_MATRIX_HD inline bool same_column(const uint64_t* K, const uint32_t* Gr, uint64_t i, uint64_t j) {
+  return K[i] == K[j] && Gr[i] == Gr[j];
+}
+GG_MATRIX_HD inline bool in_column(const uint64_t* K, const uint32_t* Gr, uint64_t i, uint64_t ne) {
+  return (i > 0 && same_column(K, Gr, i, i - 1)) || (i + 1 < ne && same_column(K, Gr, i + 1, i));
+}
+GG_MATRIX_HD inline bool column_head(const uint64_t* K, const uint32_t* Gr, uint64_t i, uint64_t ne) {
+  return (i == 0 || !same_column(K, Gr, i, i - 1)) && i + 1 < ne && same_column(K, Gr, i + 1, i);
+}
+GG_MATRIX_HD inline uint64_t column_flags(const uint64_t* K, const uint32_t* Gr, uint64_t i, uint64_t ne) {
+  return (uint64_t)column_head(K, Gr, i, ne) | ((uint64_t)in_column(K, Gr, i, ne) << 32);
+}
+// the first column id of the group whose first sorted entry is e0, from the inclusive sums
+GG_MATRIX_HD inline uint32_t group_first_id(const uint64_t* sums, uint64_t e0) {
+  return e0 ? (uint32_t)sums[e0 - 1] : 0u;
+}
+
+GG_MATRIX_HD inline uint32_t group_tile_pairs(uint32_t m) { return m >= 2 ? tile_pairs_of(tiles_of(m)) : 0u; }
+// the group of workgroup w: the last g with tp_off[g] <= w (w < tp_off[n_groups]; groups without workgroups are passed over)
+template <typename Ptr>
+GG_MATRIX_HD inline uint32_t group_of_workgroup(Ptr tp_off, uint32_t n_groups, uint32_t w) {
+  uint32_t lo = 0, hi = n_groups;  // tp_off[lo] <= w < tp_off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (tp_off[mid] <= w) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// the group of position p: the last g with offsets[g] <= p (p < offsets[n_groups]; empty groups are passed over)
+template <typename Ptr>
+GG_MATRIX_HD inline uint32_t group_of_position(Ptr offsets, uint32_t n_groups, uint32_t p) {
+  return group_of_workgroup(offsets, n_groups, p);
+}
+
+// The limits of one grouped call: P s < 2^31 sketch slots, fewer than 2^32
+// cells, fewer than 2^31 workgroups.  (group_tile_pairs(m) <= m^2 / 4, so the
+// cells' limit is always the first of the last two to break.)
+inline bool group_limits_ok(uint64_t positions, uint64_t sketch_size, uint64_t cells, uint64_t tile_pairs) {
+  return positions * sketch_size < (1ull << 31) && cells < (1ull << 32) && tile_pairs < (1ull << 31);
+}
+// cell_off[0 .. n_groups] and tp_off[0 .. n_groups] (either may be null) of
+// ascending offsets; false when a limit is broken (sketch_size 1: the
+// positions alone)
+inline bool group_layout(const uint32_t* offsets, uint32_t n_groups, uint64_t sketch_size, uint64_t* cell_off,
+                         uint32_t* tp_off) {
+  uint64_t cells = 0, pairs = 0;
+  for (uint32_t g = 0; g <= n_groups; ++g) {
+    if (cell_off) cell_off[g] = cells;
+    if (tp_off) tp_off[g] = (uint32_t)pairs;
+    if (g == n_groups) break;
+    const uint64_t m = offsets[g + 1] - offsets[g];
+    cells += m * m;
+    pairs += m < (1ull << 16) ? group_tile_pairs((uint32_t)m) : (1ull << 31);
+    if (!group_limits_ok(offsets[g + 1], sketch_size, cells, pairs)) return false;
+  }
+  return true;
+}
+
+// The columns of every group on the host: piece[p] the ascending group-local
+// column ids of position p, first_id[g] the group's first id.
+struct GroupColumns {
+  uint64_t n_entries = 0, n_columns = 0, column_entries = 0;
+  std::vector<std::vector<uint32_t>> piece;
+  std::vector<uint32_t> first_id;
+};
+inline GroupColumns columns_host(const uint64_t* sketches, const uint32_t* lens, uint32_t sketch_size,
+                                 const uint32_t* members, const uint32_t* offsets, uint32_t n_groups) {
+  struct Key {
+    uint32_t group;
+    uint64_t hash;
+    uint64_t slot;
+  };
+  const uint32_t P = offsets[n_groups];
+  std::vector<Key> keys;
+  std::vector<uint64_t> first_entry(n_groups + 1, 0);
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    first_entry[g] = keys.size();
+    for (uint32_t p = offsets[g]; p < offsets[g + 1]; ++p) {
+      const uint32_t row = members[p];
+      for (uint32_t e = 0; e < lens[row]; ++e)
+        keys.push_back(Key{g, sketches[(size_t)row * sketch_size + e], (uint64_t)p * sketch_size + e});
+    }
+  }
+  first_entry[n_groups] = keys.size();
+  std::stable_sort(keys.begin(), keys.end(), [](const Key& x, const Key& y) {
+    return x.group != y.group ? x.group < y.group : x.hash < y.hash;
+  });
+  std::vector<uint64_t> K(keys.size()), sums(keys.size());
+  std::vector<uint32_t> Gr(keys.size());
+  for (size_t i = 0; i < keys.size(); ++i) {
+    K[i] = keys[i].hash;
+    Gr[i] = keys[i].group;
+  }
+  GroupColumns c;
+  c.n_entries = K.size();
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < K.size(); ++i) sums[i] = sum += column_flags(K.data(), Gr.data(), i, K.size());
+  c.first_id.resize(n_groups);
+  for (uint32_t g = 0; g < n_groups; ++g) c.first_id[g] = group_first_id(sums.data(), first_entry[g]);
+  std::vector<uint32_t> id_of((size_t)P * sketch_size, kNoColumn);
+  for (uint64_t i = 0; i < K.size(); ++i)
+    if (in_column(K.data(), Gr.data(), i, K.size()))
+      id_of[keys[i].slot] = column_id(sums[i]) - group_first_id(sums.data(), first_entry[Gr[i]]);
+  c.n_columns = (uint32_t)sum;
+  c.column_entries = sum >> 32;
+  c.piece.resize(P);
+  for (uint32_t p = 0; p < P; ++p)
+    for (uint32_t e = 0; e < lens[members[p]]; ++e)
+      if (id_of[(size_t)p * sketch_size + e] != kNoColumn) c.piece[p].push_back(id_of[(size_t)p * sketch_size + e]);
+  return c;
+}
+
 }  // namespace matrix
 }  // namespace gg

@@ -1173,6 +1173,133 @@ gg_status gg_cluster_files_resident(gg_ctx* ctx, const char* const* paths, uint3
   return GG_OK;
 }
 
+gg_status gg_precluster_matrices_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                       const char* cache_dir, uint32_t** members, uint32_t** offsets,
+                                       uint32_t* n_groups, uint64_t** cell_offsets, uint32_t** common,
+                                       uint32_t** total, float** ani, gg_matrix_summary* summary) {
+  const char* who = "gg_precluster_matrices_files";
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  if (summary) *summary = gg_matrix_summary{};
+  if (!members || !offsets || !n_groups || !cell_offsets || (n_paths && !paths))
+    return fail(ctx, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (!common && !total && !ani) return fail(ctx, GG_ERR_INVALID_ARG, std::string(who) + ": no output asked for");
+  if (std::isnan(min_ani)) return fail(ctx, GG_ERR_INVALID_ARG, std::string(who) + ": min_ani is NaN");
+  *members = *offsets = nullptr;
+  *cell_offsets = nullptr;
+  *n_groups = 0;
+  if (common) *common = nullptr;
+  if (total) *total = nullptr;
+  if (ani) *ani = nullptr;
+  for (double& x : ctx->phase_ms) x = 0.0;
+  const std::vector<gg_ctx*> ms = gg::members(ctx);  // (the parameter `members` hides the function)
+  gg_ctx* m = ms[0];
+  const uint32_t n = n_paths, s = m->s;
+  std::vector<Rows> rows;
+  std::vector<RowSpan> spans;
+  // a multi-device context sketches on every member; the rows then go to the first through the host
+  std::vector<uint64_t> h_sk;
+  std::vector<uint32_t> h_len;
+  if (ms.size() > 1) {
+    h_sk.resize((size_t)std::max(n, 1u) * s);
+    h_len.resize(std::max(n, 1u));
+  }
+  auto t0 = Clock::now();
+  gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, ms.size() > 1 ? h_sk.data() : nullptr,
+                                      ms.size() > 1 ? h_len.data() : nullptr, nullptr);
+  if (st != GG_OK) return st;
+  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
+  t0 = Clock::now();
+  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+  const uint64_t* d_sk = n ? rows[0].sk : nullptr;
+  const uint32_t* d_len = n ? rows[0].len : nullptr;
+  auto run = [&]() -> gg_status {
+    if (n && ms.size() > 1) {
+      uint64_t* up_sk;
+      uint32_t* up_len;
+      GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)n * s, &up_sk));
+      GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)n, &up_len));
+      GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+      GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+      d_sk = up_sk;
+      d_len = up_len;
+    }
+    // K2, the partition of its pair list and the groups' matrices, all on the resident rows
+    gg_pair* d_pairs = nullptr;
+    uint64_t n_pairs = 0;
+    uint32_t passes = 0, n_sets = 0;
+    gg_status r = pairs_rows_device(m, who, d_sk, d_len, n, min_ani, &d_pairs, &n_pairs, &passes, m->stream);
+    if (r != GG_OK) return r;
+    uint32_t *d_members = nullptr, *d_offsets = nullptr;
+    GG_HIP(m, scratch_t(m, "rs_members", (size_t)std::max(n, 1u), &d_members));
+    GG_HIP(m, scratch_t(m, "rs_offsets", (size_t)n + 1, &d_offsets));
+    if (n) {
+      r = preclusters_device(m, n, d_pairs, n_pairs, d_members, d_offsets, &n_sets, nullptr, nullptr, m->stream);
+      if (r != GG_OK) return r;
+    }
+    *members = (uint32_t*)malloc(std::max<size_t>(n, 1) * sizeof(uint32_t));
+    *offsets = (uint32_t*)calloc((size_t)n_sets + 1, sizeof(uint32_t));
+    *cell_offsets = (uint64_t*)calloc((size_t)n_sets + 1, sizeof(uint64_t));
+    if (!*members || !*offsets || !*cell_offsets) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+    if (n) {
+      GG_HIP(m, hipMemcpyAsync(*members, d_members, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+      GG_HIP(m, hipMemcpyAsync(*offsets, d_offsets, ((size_t)n_sets + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               m->stream));
+      GG_HIP(m, hipStreamSynchronize(m->stream));
+    }
+    r = gg_ani_matrix_group_cells(*offsets, n_sets, *cell_offsets);
+    if (r != GG_OK) return fail(m, r, gg_thread_last_error());
+    const uint64_t cells = (*cell_offsets)[n_sets];
+    uint32_t *d_common = nullptr, *d_total = nullptr;
+    float* d_ani = nullptr;
+    if (common) {
+      *common = (uint32_t*)malloc(std::max<uint64_t>(cells, 1) * sizeof(uint32_t));
+      if (!*common) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+      GG_HIP(m, scratch_t(m, "mx_h_common", (size_t)cells, &d_common));
+    }
+    if (total) {
+      *total = (uint32_t*)malloc(std::max<uint64_t>(cells, 1) * sizeof(uint32_t));
+      if (!*total) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+      GG_HIP(m, scratch_t(m, "mx_h_total", (size_t)cells, &d_total));
+    }
+    if (ani) {
+      *ani = (float*)malloc(std::max<uint64_t>(cells, 1) * sizeof(float));
+      if (!*ani) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+      GG_HIP(m, scratch_t(m, "mx_h_ani", (size_t)cells, &d_ani));
+    }
+    if (cells == 0) {
+      *n_groups = n_sets;
+      return GG_OK;
+    }
+    r = ani_matrix_groups_device(m, d_sk, d_len, n, d_members, *offsets, n_sets, d_common, d_total, d_ani, summary,
+                                 m->stream);
+    if (r != GG_OK) return r;
+    if (common) GG_HIP(m, hipMemcpyAsync(*common, d_common, cells * 4, hipMemcpyDeviceToHost, m->stream));
+    if (total) GG_HIP(m, hipMemcpyAsync(*total, d_total, cells * 4, hipMemcpyDeviceToHost, m->stream));
+    if (ani) GG_HIP(m, hipMemcpyAsync(*ani, d_ani, cells * 4, hipMemcpyDeviceToHost, m->stream));
+    GG_HIP(m, hipStreamSynchronize(m->stream));
+    *n_groups = n_sets;
+    return GG_OK;
+  };
+  st = run();
+  ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
+  if (st != GG_OK) {
+    free(*members);
+    free(*offsets);
+    free(*cell_offsets);
+    *members = *offsets = nullptr;
+    *cell_offsets = nullptr;
+    for (void** p : {(void**)common, (void**)total, (void**)ani})
+      if (p) {
+        free(*p);
+        *p = nullptr;
+      }
+    *n_groups = 0;
+    if (summary) *summary = gg_matrix_summary{};
+    if (m != ctx) ctx->err = m->err;
+  }
+  return st;
+}
+
 gg_status gg_precluster_files_each(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
                                    const char* cache_dir, gg_pair_sink sink, void* user, gg_pair** pairs,
                                    float** ani, uint64_t* n_out, uint32_t* n_cached) {

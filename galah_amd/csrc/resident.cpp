@@ -18,6 +18,41 @@
 
 namespace gg {
 
+gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                            float min_ani, gg_pair** d_pairs, uint64_t* n_pairs, uint32_t* n_passes, hipStream_t st) {
+  gg_pair* d_out = nullptr;
+  uint64_t cnt = 0;
+  uint32_t passes = 0;
+  *d_pairs = nullptr;
+  *n_pairs = 0;
+  *n_passes = 0;
+  if (n < 2) return GG_OK;
+  uint64_t *d_count, *h_count;
+  GG_HIP(c, scratch_t(c, "rs_count", 1, &d_count));
+  GG_HIP(c, host_scratch_t(c, "rs_count", 1, &h_count));
+  const uint64_t all = (uint64_t)n * (n - 1) / 2;
+  uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all);
+  for (;;) {
+    if (passes == 2) return fail(c, GG_ERR_INTERNAL, std::string(who) + ": pair output sizing failed");
+    GG_HIP(c, scratch_t(c, "rs_pairs", (size_t)cap, &d_out));
+    GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+    const gg_status ps = pairs_core(c, d_sk, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, cap, d_count, st);
+    if (ps != GG_OK) return ps;
+    ++passes;
+    GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    GG_HIP(c, hipStreamSynchronize(st));
+    cnt = *h_count;
+    if (cnt > all) return fail(c, GG_ERR_INTERNAL, std::string(who) + ": bad pair count");
+    if (cnt <= cap) break;
+    cap = cnt;
+  }
+  if (cnt >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 pairs or more");
+  *d_pairs = d_out;
+  *n_pairs = cnt;
+  *n_passes = passes;
+  return GG_OK;
+}
+
 gg_status cluster_rows_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, float min_ani,
                               float T, uint32_t* d_rep_of, gg_cluster_summary* sum, const gg_pair** d_pairs,
                               const float** d_ani, hipStream_t st) {
@@ -29,31 +64,11 @@ gg_status cluster_rows_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d
   float* d_val = nullptr;
   uint64_t cnt = 0;
   uint32_t passes = 0;
-  if (n >= 2) {
-    uint64_t *d_count, *h_count;
-    GG_HIP(c, scratch_t(c, "rs_count", 1, &d_count));
-    GG_HIP(c, host_scratch_t(c, "rs_count", 1, &h_count));
-    const uint64_t all = (uint64_t)n * (n - 1) / 2;
-    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all);
-    for (;;) {
-      if (passes == 2) return fail(c, GG_ERR_INTERNAL, "gg_cluster_rows_device: pair output sizing failed");
-      GG_HIP(c, scratch_t(c, "rs_pairs", (size_t)cap, &d_out));
-      GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-      const gg_status ps = pairs_core(c, d_sk, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, cap, d_count, st);
-      if (ps != GG_OK) return ps;
-      ++passes;
-      GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      GG_HIP(c, hipStreamSynchronize(st));
-      cnt = *h_count;
-      if (cnt > all) return fail(c, GG_ERR_INTERNAL, "gg_cluster_rows_device: bad pair count");
-      if (cnt <= cap) break;
-      cap = cnt;
-    }
-    if (cnt >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, "gg_cluster_rows_device: 2^31 pairs or more");
-  }
+  gg_status s = pairs_rows_device(c, "gg_cluster_rows_device", d_sk, d_lens, n, min_ani, &d_out, &cnt, &passes, st);
+  if (s != GG_OK) return s;
   uint64_t rechecked = 0;
   GG_HIP(c, scratch_t(c, "rs_ani", (size_t)std::max<uint64_t>(cnt, 1), &d_val));
-  gg_status s = ani_f32_device(c, d_out, cnt, d_val, nullptr, &rechecked, st);
+  s = ani_f32_device(c, d_out, cnt, d_val, nullptr, &rechecked, st);
   if (s != GG_OK) return s;
   s = cluster_device(c, n, d_out, d_val, cnt, T, d_rep_of, st);
   if (s != GG_OK) return s;

@@ -462,6 +462,47 @@ inline std::vector<float> ani_matrix(const std::vector<std::string>& paths, size
   return out;
 }
 
+// The finch ANI table of every precluster of the genomes
+// (gg_precluster_matrices_files): the files sketched once, the preclusters at
+// precluster_ani (a fraction) and each one's dense matrix in one grouped call
+// on the GPU.  Largest precluster first; a block is row-major [m x m] over
+// `indices` (into paths, ascending).
+struct PreclusterAniMatrix {
+  std::vector<size_t> indices;
+  std::vector<float> ani;
+};
+inline std::vector<PreclusterAniMatrix> precluster_ani_matrices(const std::vector<std::string>& paths,
+                                                                float precluster_ani = 0.9f, size_t num_kmers = 1000,
+                                                                uint8_t kmer_length = 21,
+                                                                const char* sketch_cache_dir = nullptr) {
+  std::vector<PreclusterAniMatrix> out;
+  if (paths.empty()) return out;
+  std::vector<const char*> c_paths;
+  for (const auto& p : paths) c_paths.push_back(p.c_str());
+  gg_status st = GG_OK;
+  gg_ctx* ctx = gg_create_multi(kmer_length, (uint32_t)num_kmers, 0, nullptr, 0, &st);
+  if (!ctx) throw std::runtime_error(std::string("Failed to sketch genomes with finch: ") + gg_thread_last_error());
+  gg_set_host_threads(ctx, current_num_threads());
+  uint32_t *members = nullptr, *offsets = nullptr, n_groups = 0;
+  uint64_t* cells = nullptr;
+  float* ani = nullptr;
+  st = gg_precluster_matrices_files(ctx, c_paths.data(), (uint32_t)c_paths.size(), precluster_ani, sketch_cache_dir,
+                                    &members, &offsets, &n_groups, &cells, nullptr, nullptr, &ani, nullptr);
+  const std::string msg = st != GG_OK ? gg_last_error(ctx) : "";
+  gg_destroy(ctx);
+  if (st != GG_OK) throw std::runtime_error("Failed to sketch genomes with finch: " + msg);  // src/finch.rs:50
+  out.resize(n_groups);
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    out[g].indices.assign(members + offsets[g], members + offsets[g + 1]);
+    out[g].ani.assign(ani + cells[g], ani + cells[g + 1]);
+  }
+  gg_free(members);
+  gg_free(offsets);
+  gg_free(cells);
+  gg_free(ani);
+  return out;
+}
+
 // src/genome_stats.rs:4-9 (#[derive(Debug, PartialEq)])
 struct GenomeAssemblyStats {
   size_t num_contigs;

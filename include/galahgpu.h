@@ -616,6 +616,57 @@ gg_status gg_ani_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const ui
 gg_status gg_ani_matrix_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, const char* cache_dir,
                               uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary);
 
+/* ---- dense ANI matrices of many groups in one call ------ */
+/* The matrix above for every group of a CSR at once -- the preclusters of a
+ * run, as gg_preclusters returns them: group g is members[offsets[g] ..
+ * offsets[g+1]), row indices in any order; a row may be listed twice in a
+ * group and in several groups, a group may be empty; offsets[0] == 0 and
+ * offsets ascend.  Block g is the [m_g x m_g] row-major matrix of the group's
+ * rows, by the rules above, and begins at cell_offsets[g] = the sum of m_h^2
+ * over h < g; there are no cells between groups and no cap on the number of
+ * rows.  One call: P = offsets[n_groups] positions with P * sketch size <
+ * 2^31, fewer than 2^32 cells, fewer than 2^31 64 x 64 tile pairs; else
+ * GG_ERR_INVALID_ARG.  The summary's counts are summed over the groups (a
+ * column is a hash held at two or more positions of one group). */
+
+/* cell_offsets[0 .. n_groups] of the offsets, cell_offsets[n_groups] the
+ * number of cells; host arithmetic, no ctx.  GG_ERR_INVALID_ARG for offsets
+ * that do not begin at 0 or do not ascend and for the limits above (the
+ * sketch size taken as 1). */
+gg_status gg_ani_matrix_group_cells(const uint32_t* offsets, uint32_t n_groups, uint64_t* cell_offsets);
+/* On the host (the merge itself per unordered pair of each group, mirrored);
+ * no device, no ctx.  common / total / ani hold cell_offsets[n_groups]
+ * entries, each may be NULL. */
+gg_status gg_ani_matrix_groups_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                                    int kmer_length, const uint32_t* members, const uint32_t* offsets,
+                                    uint32_t n_groups, uint32_t* common, uint32_t* total, float* ani);
+/* The same on the context's (first) device: host arrays in and out.  The
+ * host-input forms return GG_ERR_INVALID_ARG for an index >= n, lens[g] >
+ * sketch_size or all three outputs NULL. */
+gg_status gg_ani_matrix_groups(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                               const uint32_t* members, const uint32_t* offsets, uint32_t n_groups,
+                               uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary);
+/* Device-resident rows, members and outputs on the given stream; offsets is a
+ * host array (the library shapes its launches from the sizes).  Synchronises
+ * the stream.  The members are not checked: an index >= n is an empty row. */
+gg_status gg_ani_matrix_groups_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                      const uint32_t* d_members, const uint32_t* offsets, uint32_t n_groups,
+                                      uint32_t* d_common, uint32_t* d_total, float* d_ani,
+                                      gg_matrix_summary* summary, void* stream);
+/* The ANI matrix of every precluster of a file list: the files sketched as
+ * gg_precluster_files_cached does, then, with the rows resident, K2 at
+ * min_ani, gg_preclusters_device over the pair list in device memory and the
+ * grouped matrices; only the results are copied back.  *members [n_paths],
+ * *offsets and *cell_offsets [*n_groups + 1], *common / *total / *ani
+ * [(*cell_offsets)[*n_groups]] are library-owned (gg_free); each of common /
+ * total / ani may be NULL, not all three.  The groups are gg_preclusters':
+ * largest first, members ascending.  A multi-device context sketches on every
+ * member and runs the rest on its first. */
+gg_status gg_precluster_matrices_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                       const char* cache_dir, uint32_t** members, uint32_t** offsets,
+                                       uint32_t* n_groups, uint64_t** cell_offsets, uint32_t** common,
+                                       uint32_t** total, float** ani, gg_matrix_summary* summary);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);

@@ -343,6 +343,24 @@ extern "C" {
                                common: *mut u32, total: *mut u32, ani: *mut f32, summary: *mut gg_matrix_summary)
         -> GgStatus;
 
+    // dense ANI matrices of many groups in one call
+    pub fn gg_ani_matrix_group_cells(offsets: *const u32, n_groups: u32, cell_offsets: *mut u64) -> GgStatus;
+    pub fn gg_ani_matrix_groups_host(sketches: *const u64, lens: *const u32, n: u32, sketch_size: u32,
+                                     kmer_length: c_int, members: *const u32, offsets: *const u32, n_groups: u32,
+                                     common: *mut u32, total: *mut u32, ani: *mut f32) -> GgStatus;
+    pub fn gg_ani_matrix_groups(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32,
+                                members: *const u32, offsets: *const u32, n_groups: u32, common: *mut u32,
+                                total: *mut u32, ani: *mut f32, summary: *mut gg_matrix_summary) -> GgStatus;
+    pub fn gg_ani_matrix_groups_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32,
+                                       d_members: *const u32, offsets: *const u32, n_groups: u32,
+                                       d_common: *mut u32, d_total: *mut u32, d_ani: *mut f32,
+                                       summary: *mut gg_matrix_summary, stream: *mut c_void) -> GgStatus;
+    pub fn gg_precluster_matrices_files(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
+                                        cache_dir: *const c_char, members: *mut *mut u32, offsets: *mut *mut u32,
+                                        n_groups: *mut u32, cell_offsets: *mut *mut u64, common: *mut *mut u32,
+                                        total: *mut *mut u32, ani: *mut *mut f32, summary: *mut gg_matrix_summary)
+        -> GgStatus;
+
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;
     pub fn gg_ani_f32(common: u32, total: u32, kmer_length: c_int) -> f32;
