@@ -72,6 +72,8 @@ EXPORTED_SYMBOLS = (
     "gg_ani_matrix_host", "gg_ani_matrix", "gg_ani_matrix_device", "gg_ani_matrix_files",
     "gg_ani_matrix_group_cells", "gg_ani_matrix_groups_host", "gg_ani_matrix_groups", "gg_ani_matrix_groups_device",
     "gg_precluster_matrices_files",
+    "gg_pairs_matrix_device", "gg_pairs_matrix", "gg_set_pairs_path", "gg_pairs_path", "gg_pairs_paths_taken",
+    "gg_precluster_files_resident",
 )
 
 GG_OK = 0
@@ -240,6 +242,30 @@ _sig("gg_precluster_matrices_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p)
                                             ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u32),
                                             ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                             ctypes.POINTER(_vp), ctypes.POINTER(_MatrixSummary)])
+
+
+class _PairsMatrixSummary(ctypes.Structure):
+    _fields_ = [("n_entries", ctypes.c_uint64), ("n_columns", ctypes.c_uint64), ("column_entries", ctypes.c_uint64),
+                ("n_pairs", ctypes.c_uint64), ("chunk_rounds", ctypes.c_uint64), ("index_reads", ctypes.c_uint64),
+                ("path", ctypes.c_uint32), ("pair_passes", ctypes.c_uint32)]
+
+    def as_dict(self):
+        d = {f: int(getattr(self, f)) for f, _ in self._fields_}
+        d["path"] = PAIRS_PATHS[d["path"]]
+        return d
+
+
+PAIRS_PATHS = ("default", "matrix", "auto")  # GG_PAIRS_PATH_*
+_sig("gg_pairs_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, ctypes.c_float, _vp, _u64, _vp,
+                                      ctypes.POINTER(_PairsMatrixSummary), _vp])
+_sig("gg_pairs_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp),
+                               ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
+_sig("gg_set_pairs_path", _i32, [_vp, _i32])
+_sig("gg_pairs_path", _i32, [_vp])
+_sig("gg_pairs_paths_taken", _i32, [_vp, _vp])
+_sig("gg_precluster_files_resident", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
+                                            ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                            ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
 
 
 class _Validation(ctypes.Structure):
@@ -1126,6 +1152,71 @@ class Context:
             raise self._err(st)
         return self._pairs_ani(pp, ap, cnt.value)
 
+    def precluster_files_resident(self, paths, min_ani, cache_dir=None):
+        """precluster_files with the rows resident on the (first) device
+        (gg_precluster_files_resident): the pairs by the context's pairs path
+        (set_pairs_path), sorted and given their f32 ANI on the device ->
+        (pairs, ani, summary dict of gg_pairs_matrix_summary).  pairs and ani
+        equal precluster_files' whatever the path."""
+        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        summary = _PairsMatrixSummary()
+        st = _L.gg_precluster_files_resident(self._c, arr, len(paths), ctypes.c_float(min_ani),
+                                             None if cache_dir is None else os.fsencode(cache_dir),
+                                             ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt),
+                                             ctypes.byref(summary))
+        if st != GG_OK:
+            raise self._err(st)
+        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
+        return pairs, ani, summary.as_dict()
+
+    def pairs_matrix(self, sketches, lens, min_ani, rows=None):
+        """pairs() over the listed rows (None: all of them) by the matrix
+        product with the thresholded epilogue (gg_pairs_matrix, DESIGN.md
+        4.12): for dense sets, where the inverted index pays g^2 reads per
+        hash shared by g rows -> (pairs sorted by (i, j), summary dict of
+        gg_pairs_matrix_summary).  rows may not repeat an index."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        if rows is None:
+            r, rp, m = None, None, n
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.uint32)
+            rp, m = _ptr(r), len(r)
+        outp, cnt = _vp(), _u64()
+        summary = _PairsMatrixSummary()
+        st = _L.gg_pairs_matrix(self._c, _ptr(sk), _ptr(ln), n, rp, m, ctypes.c_float(min_ani), ctypes.byref(outp),
+                                ctypes.byref(cnt), ctypes.byref(summary))
+        if st != GG_OK:
+            raise self._err(st)
+        return _take_pairs(outp, cnt.value), summary.as_dict()
+
+    def set_pairs_path(self, path):
+        """What produces the pairs inside cluster_rows_device,
+        cluster_files_resident, precluster_matrices_files and
+        precluster_files_resident: "default" (K2), "matrix" (the pair form of
+        the matrix product) or "auto" (the product when the index is certainly
+        the dearer, gg_set_pairs_path) -> the path that was set before."""
+        if path not in PAIRS_PATHS:
+            raise ValueError("pairs path must be one of %s, not %r" % (", ".join(PAIRS_PATHS), path))
+        before = self.pairs_path
+        st = _L.gg_set_pairs_path(self._c, PAIRS_PATHS.index(path))
+        if st != GG_OK:
+            raise self._err(st)
+        return before
+
+    @property
+    def pairs_path(self):
+        return PAIRS_PATHS[_L.gg_pairs_path(self._c)]
+
+    def pairs_paths_taken(self):
+        """Calls that needed pairs of resident rows since creation, by what
+        ran: {"default", "matrix", "auto"} (auto: the matrix by AUTO's choice)."""
+        c = np.zeros(3, np.uint64)
+        st = _L.gg_pairs_paths_taken(self._c, _ptr(c))
+        if st != GG_OK:
+            raise self._err(st)
+        return {k: int(v) for k, v in zip(PAIRS_PATHS, c)}
+
     def cluster_pairs(self, n_genomes, pairs, ani, cluster_ani):
         """cluster_pairs_host on the context's (first) device -> rep_of."""
         p, a = _pairs_ani_arg(pairs, ani)
@@ -1451,6 +1542,25 @@ class Context:
         if st != GG_OK:
             raise self._err(st)
 
+    def pairs_matrix_device(self, d_sketches, d_lens, n, d_rows, m, min_ani, d_out, out_cap, d_count,
+                            want_summary=True, stream=None):
+        """pairs_matrix over device-resident tensors, the output contract of
+        pairs_device: the passing pairs among the m listed rows (d_rows None:
+        rows 0 .. m-1) appended unsorted to d_out, d_count (u64) grown by the
+        number found, nothing written past out_cap.  d_rows is not checked: an
+        index >= n is an empty row, a row listed twice gets its pairs once per
+        position.  Synchronises the stream -> summary dict (None without
+        want_summary; n_pairs may exceed out_cap)."""
+        summary = _PairsMatrixSummary()
+        st = _L.gg_pairs_matrix_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n,
+                                       None if d_rows is None else _dev_ptr(d_rows), m, ctypes.c_float(min_ani),
+                                       _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
+                                       ctypes.byref(summary) if want_summary else None,
+                                       None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+        return summary.as_dict() if want_summary else None
+
     def ani_matrix_device(self, d_sketches, d_lens, n, d_rows, m, d_common=None, d_total=None, d_ani=None,
                           stream=None):
         """ani_matrix over device-resident tensors: d_sketches [n, s] u64,
@@ -1612,10 +1722,15 @@ def _context(k, s, seed=0):
     return c
 
 
-def distances(genome_fasta_paths, min_ani, num_kmers, kmer_length, sketch_cache_dir=None):
+def distances(genome_fasta_paths, min_ani, num_kmers, kmer_length, sketch_cache_dir=None, pairs_path=None):
     """src/finch.rs:26-75 -> SortedPairGenomeDistanceCache, computed on the GPU.
     sketch_cache_dir (not in galah) reuses sketches of
-    unchanged genome files from earlier runs; the result is the same."""
+    unchanged genome files from earlier runs; the result is the same.
+    pairs_path ("default", "matrix" or "auto"; None: the call below as ever)
+    takes Context.precluster_files_resident under that path on a one-device
+    context.  It is ignored, the result being the same, at debug level (every
+    compared pair must be logged: the streaming call stays) and on a
+    multi-device context (the resident call is not sharded)."""
     log = logging.getLogger("galah")
     # At debug level the reference logs every compared pair
     # (src/finch.rs:65-68): the library then streams all N (N - 1) / 2 pairs
@@ -1638,6 +1753,12 @@ def distances(genome_fasta_paths, min_ani, num_kmers, kmer_length, sketch_cache_
         thr = float(np.float32(min_ani))
         if every:
             pairs, ani = ctx.precluster_files_each(paths, thr, each, cache_dir=sketch_cache_dir)
+        elif pairs_path is not None and ctx.device_count == 1:
+            before = ctx.set_pairs_path(pairs_path)  # (the cached context is shared: put back what was set)
+            try:
+                pairs, ani, _ = ctx.precluster_files_resident(paths, thr, cache_dir=sketch_cache_dir)
+            finally:
+                ctx.set_pairs_path(before)
         else:
             pairs, ani = ctx.precluster_files(paths, thr, cache_dir=sketch_cache_dir)
     except GalahGpuError as e:
@@ -1681,15 +1802,30 @@ def rust_f64(x):
 class FinchPreclusterer(PreclusterDistanceFinder):
     """src/finch.rs:4-24: min_ani is a fraction (f32), num_kmers = s, kmer_length = k."""
 
-    def __init__(self, min_ani, num_kmers=1000, kmer_length=21, sketch_cache_dir=None):
+    def __init__(self, min_ani, num_kmers=1000, kmer_length=21, sketch_cache_dir=None, pairs_path=None):
+        """pairs_path: None (the default K2 through the calls used so far),
+        or "default" / "matrix" / "auto": distances() and cluster() then run
+        the resident calls under that pairs path (Context.set_pairs_path;
+        "matrix" suits thousands of strains of one species).  The results do
+        not depend on it.  It is ignored on a multi-device context and, in
+        distances(), at debug level (see distances).  The path is set on the
+        shared cached context around the call and put back after it: two
+        threads with different pairs paths can switch each other's route (and
+        what pairs_paths_taken counts) mid-call, never a result."""
+        if pairs_path is not None and pairs_path not in PAIRS_PATHS:
+            raise ValueError("pairs_path must be None or one of %s, not %r" % (", ".join(PAIRS_PATHS), pairs_path))
         self.min_ani = np.float32(min_ani)
         self.num_kmers = int(num_kmers)
         self.kmer_length = int(kmer_length)
         self.sketch_cache_dir = sketch_cache_dir
+        self.pairs_path = pairs_path
 
     def distances(self, genome_fasta_paths):
+        if self.pairs_path is None:
+            return distances(genome_fasta_paths, self.min_ani, self.num_kmers, self.kmer_length,
+                             sketch_cache_dir=self.sketch_cache_dir)
         return distances(genome_fasta_paths, self.min_ani, self.num_kmers, self.kmer_length,
-                         sketch_cache_dir=self.sketch_cache_dir)
+                         sketch_cache_dir=self.sketch_cache_dir, pairs_path=self.pairs_path)
 
     def method_name(self):
         return "finch"
@@ -1912,7 +2048,15 @@ def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
         if ctx.device_count == 1:
             # one device: the pair list stays in its memory, the preclusters'
             # count and largest size come back with rep_of
-            rep_of, summary = ctx.cluster_files_resident(paths, min_ani, T, cache_dir=cache_dir)
+            pairs_path = getattr(preclusterer, "pairs_path", None)
+            if pairs_path is None:
+                rep_of, summary = ctx.cluster_files_resident(paths, min_ani, T, cache_dir=cache_dir)
+            else:
+                before = ctx.set_pairs_path(pairs_path)  # (the cached context is shared: put back what was set)
+                try:
+                    rep_of, summary = ctx.cluster_files_resident(paths, min_ani, T, cache_dir=cache_dir)
+                finally:
+                    ctx.set_pairs_path(before)
             n_sets, largest = summary["n_preclusters"], summary["largest_precluster"]
         else:
             rep_of, pairs, _ = ctx.cluster_files(paths, min_ani, T, cache_dir=cache_dir)

@@ -41,9 +41,21 @@
 // The matrices of many groups in one call are further down:
 // the same product kernel instantiated on MxGroupLaunch, fed by entries sorted
 // by (group, hash) with column ids local to a group.
+//
+// The pair form is the third instantiation, on MxPairLaunch:
+// the same prologue, chunk loop and accumulators, and instead of the dense
+// epilogue the thresholded one of matrix_core.hpp -- a tile pair that ran no
+// chunk returns at once (unless pairs without a shared hash pass), a cell pays
+// the rank search only when its common can pass, and the passing pairs are
+// staged in the image area (free after the loop's last barrier), counted with
+// one LDS add per wave and step, and appended to the output with one global
+// add per workgroup and 16-byte stores.  matrix_prepare is the positions part
+// shared by the dense and the pair form; beyond kMaxRows rows (the pair form
+// only) the offsets come from mxp_positions_kernel and a scan.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -64,13 +76,20 @@ using matrix::kRowBytes;
 using matrix::kTile;
 using matrix::kTileBytes;
 
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;  // a position whose row index is out of range: the one empty row
 constexpr uint32_t kOffBlock = 1024;
 constexpr uint32_t kOffPer = matrix::kMaxRows / kOffBlock;  // positions per thread of mx_offsets_kernel
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 inline dim3 grid_for(uint64_t items) { return dim3((uint32_t)std::min<uint64_t>(16384, (items + 255) / 256)); }
+
+// GALAHGPU_TEST_PAIRS_SLICE, read per call: fewer tile pairs per launch of the pair form (tests of the slices at small m)
+uint32_t test_pair_slice() {
+  const char* e = getenv("GALAHGPU_TEST_PAIRS_SLICE");
+  if (!e || !*e) return matrix::kPairSlice;
+  return (uint32_t)std::min<uint64_t>(matrix::kPairSlice, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
+}
 
 // pos_row[a] (kNoRow: an index >= n, an empty row), pos_len[a], pos_off[0 .. m] the exclusive sum of the lengths
 __global__ __launch_bounds__(kOffBlock) void mx_offsets_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
@@ -103,6 +122,28 @@ __global__ __launch_bounds__(kOffBlock) void mx_offsets_kernel(const uint32_t* _
     off += pos_len[a];
   }
   if (t == kOffBlock - 1) pos_off[m] = part[t];
+}
+
+// the same rows and lengths for any number of positions (the pair form beyond
+// kMaxRows): len1[0 .. m] the lengths and a 0 behind them, for the scan that
+// gives pos_off
+__global__ __launch_bounds__(256) void mxp_positions_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
+                                                            const uint32_t* __restrict__ rows, uint32_t m,
+                                                            uint32_t* __restrict__ pos_row,
+                                                            uint32_t* __restrict__ pos_len,
+                                                            uint32_t* __restrict__ len1) {
+  for (uint32_t a = blockIdx.x * 256 + threadIdx.x; a <= m; a += gridDim.x * 256) {
+    if (a == m) {
+      len1[a] = 0;
+      continue;
+    }
+    const uint32_t g = rows ? rows[a] : a;
+    const bool ok = g < n;
+    const uint32_t len = ok ? min(lens[g], s) : 0u;
+    pos_row[a] = ok ? g : kNoRow;
+    pos_len[a] = len;
+    len1[a] = len;
+  }
 }
 
 __global__ __launch_bounds__(256) void mx_keys_kernel(const uint64_t* __restrict__ sk, uint32_t s, uint32_t m,
@@ -183,6 +224,7 @@ struct MxLaunch {
   uint64_t cap;
   unsigned long long* count;
   static constexpr bool kGroups = false;
+  static constexpr bool kPairs = false;
 };
 // the grouped form (matrix_core.hpp, groups): m is not read, a workgroup finds its group in tp_off
 struct MxGroupLaunch : MxLaunch {
@@ -191,6 +233,18 @@ struct MxGroupLaunch : MxLaunch {
   const uint64_t* cell_off;  // [n_groups + 1] first cell of a group's block
   uint32_t n_groups;
   static constexpr bool kGroups = true;
+};
+// the pair form (matrix_core.hpp, the pair form): common / total / ani / list are
+// not read, the passing pairs are appended to out and counted in `count`
+struct MxPairLaunch : MxLaunch {
+  const uint32_t* cmin;    // [tmax + 1]
+  const uint32_t* sufmin;  // [tmax + 1]
+  uint32_t tmax;
+  uint32_t zero_passes;
+  gg_pair* out;
+  uint64_t out_cap;
+  uint32_t wg_base;  // the tile pair of the launch's workgroup 0 (a call is launched in slices)
+  static constexpr bool kPairs = true;
 };
 
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
@@ -218,6 +272,8 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
     m = a.offsets[g + 1] - p0;
     c0 = a.cell_off[g];
     matrix::tile_pair_of(blockIdx.x - a.tp_off[g], &ti, &tj);
+  } else if constexpr (L::kPairs) {
+    matrix::tile_pair_of(a.wg_base + blockIdx.x, &ti, &tj);  // (< 2^31: pair_limits_ok)
   } else {
     matrix::tile_pair_of(blockIdx.x, &ti, &tj);
   }
@@ -242,6 +298,7 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
   const uint8_t* img_a = image;
   const uint8_t* img_b = image + (diag ? 0u : kTileBytes);
   uint32_t k0 = 0;  // (every branch on k0, s_min is the workgroup's)
+  [[maybe_unused]] bool ran = false;  // (the pair form) a chunk was run
   for (;;) {
     if (t < 2 * kTile) {  // waves 0 and 1: a tile each
       uint32_t next = kNoColumn;
@@ -293,7 +350,57 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
       }
     }
     k0 += kChunk;
+    if constexpr (L::kPairs) ran = true;
     __syncthreads();
+  }
+
+  if constexpr (L::kPairs) {
+    // The pair epilogue.  The image area is free after the loop's last
+    // barrier: the passing pairs of the tile pair (at most kPairStage) are
+    // staged there, a wave taking its slots with one LDS add per step; then
+    // one add to the global count for the workgroup and 16-byte stores.
+    __shared__ uint32_t s_found;
+    __shared__ unsigned long long s_base;
+    if (matrix::pair_early_exit(ran, a.zero_passes != 0)) return;  // (the workgroup's)
+    gg_pair* stage = reinterpret_cast<gg_pair*>(image);
+    if (t == 0) s_found = 0;
+    __syncthreads();
+    const uint32_t sb = diag ? 0u : kTile;  // tile tj's row state
+#pragma unroll
+    for (uint32_t nb = 0; nb < 4; ++nb) {
+#pragma unroll
+      for (uint32_t reg = 0; reg < 4; ++reg) {
+        const uint32_t ra = wave * 16 + matrix::cd_row(lane, reg), rb = nb * 16 + matrix::cd_col(lane);
+        const uint32_t pa = ti * kTile + ra, pb = tj * kTile + rb;
+        uint32_t common = 0, total = 0, ga = 0, gb = 0;
+        bool pass = false;
+        if (pa < m && pb < m) {
+          ga = s_row[ra];
+          gb = s_row[sb + rb];
+          if (matrix::pair_visited(pa, pb, ga, gb))
+            pass = matrix::pair_cell(a.sk + (uint64_t)ga * a.s, s_len[ra], s_last[ra], a.sk + (uint64_t)gb * a.s,
+                                     s_len[sb + rb], s_last[sb + rb], (uint32_t)acc[nb][reg], a.cmin, a.sufmin, a.tmax,
+                                     &common, &total);
+        }
+        const unsigned long long mk = __ballot(pass);
+        if (mk) {
+          const uint32_t first = (uint32_t)__builtin_ctzll(mk);
+          uint32_t at = 0;
+          if (lane == first) at = atomicAdd(&s_found, (uint32_t)__popcll(mk));
+          at = (uint32_t)__shfl((int)at, (int)first);
+          if (pass) stage[at + lanes_below(mk)] = gg_pair{min(ga, gb), max(ga, gb), common, total};
+        }
+      }
+    }
+    __syncthreads();
+    const uint32_t found = s_found;
+    if (found == 0) return;
+    if (t == 0) s_base = atomicAdd(a.count, (unsigned long long)found);
+    __syncthreads();
+    const unsigned long long base = s_base;
+    for (uint32_t i = t; i < found; i += 256)
+      if (base + i < a.out_cap) a.out[base + i] = stage[i];
+    return;
   }
 
   // epilogue: wave w holds rows 16 w .. 16 w + 15 of tile ti against the 64 positions of tile tj
@@ -345,15 +452,14 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
 
 }  // namespace
 
-gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
-                            uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
-                            hipStream_t st) {
-  if (sum) *sum = gg_matrix_summary{};
-  if (m == 0) return GG_OK;
+// The positions part of a call, up to the one read-back before the product:
+// pos_row / pos_len / piece / piece_cnt in context scratch and the three counts.
+// m s < 2^31 (the caller's check).  m <= kMaxRows: mx_offsets_kernel; more rows
+// (the pair form only): mxp_positions_kernel and a scan.  Synchronises st.
+gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st) {
   const uint32_t s = c->s;
-  const uint64_t N64 = (uint64_t)m * s;
-  if (N64 >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, "gg_ani_matrix: 2^31 sketch slots or more");
-  const uint32_t N = (uint32_t)N64;
+  const uint32_t N = (uint32_t)((uint64_t)m * s);
   uint32_t *pos_row, *pos_len, *pos_off, *vals_in, *vals_out, *piece, *piece_cnt;
   uint64_t *keys_in, *keys_out, *sums, *h_back;
   GG_HIP(c, scratch_t(c, "mx_pos", (size_t)4 * m + 1, &pos_row));
@@ -367,21 +473,34 @@ gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_l
   GG_HIP(c, scratch_t(c, "mx_vals_out", (size_t)N, &vals_out));
   GG_HIP(c, scratch_t(c, "mx_piece", (size_t)N, &piece));
   GG_HIP(c, host_scratch_t(c, "mx_back", 2, &h_back));
-  size_t sort_bytes = 0, scan_bytes = 0;
+  size_t sort_bytes = 0, scan_bytes = 0, off_bytes = 0;
   GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                                (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, 64));
   GG_HIP(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N));
-  const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
+  if (m > matrix::kMaxRows)
+    GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, off_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                               (int)(m + 1)));
+  const size_t tmp_bytes = std::max(std::max(sort_bytes, scan_bytes), off_bytes);
   uint8_t* tmp;
   GG_HIP(c, scratch_t(c, "mx_tmp", std::max<size_t>(tmp_bytes, 1), &tmp));
 
-  hipLaunchKernelGGL(mx_offsets_kernel, dim3(1), dim3(kOffBlock), 0, st, d_lens, n, s, d_rows, m, pos_row, pos_len,
-                     pos_off);
-  GG_HIP(c, hipGetLastError());
+  size_t bytes = tmp_bytes;
+  if (m <= matrix::kMaxRows) {
+    hipLaunchKernelGGL(mx_offsets_kernel, dim3(1), dim3(kOffBlock), 0, st, d_lens, n, s, d_rows, m, pos_row, pos_len,
+                       pos_off);
+    GG_HIP(c, hipGetLastError());
+  } else {
+    uint32_t* len1;  // the m lengths and a 0 behind them: the scan's last item is the number of entries
+    GG_HIP(c, scratch_t(c, "mxp_len1", (size_t)m + 1, &len1));
+    hipLaunchKernelGGL(mxp_positions_kernel, grid_for((uint64_t)m + 1), dim3(256), 0, st, d_lens, n, s, d_rows, m,
+                       pos_row, pos_len, len1);
+    GG_HIP(c, hipGetLastError());
+    GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)len1, pos_off, (int)(m + 1), st));
+  }
   hipLaunchKernelGGL(mx_keys_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, m, pos_row, pos_len, pos_off, keys_in,
                      vals_in);
   GG_HIP(c, hipGetLastError());
-  size_t bytes = tmp_bytes;
+  bytes = tmp_bytes;
   GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
                                                vals_out, (int)N, 0, 64, st));
   uint64_t* flags = keys_in;  // (the sort's input is free)
@@ -400,7 +519,23 @@ gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_l
   GG_HIP(c, hipStreamSynchronize(st));
   const uint64_t n_columns = (uint32_t)h_back[0], column_entries = h_back[0] >> 32, n_entries = (uint32_t)h_back[1];
   if (n_entries > N || column_entries > n_entries || 2 * n_columns > column_entries)
-    return fail(c, GG_ERR_INTERNAL, "gg_ani_matrix: bad column counts");
+    return fail(c, GG_ERR_INTERNAL, std::string(who) + ": bad column counts");
+  *out = MatrixPrep{pos_row, pos_len, piece, piece_cnt, m, n_entries, n_columns, column_entries};
+  return GG_OK;
+}
+
+gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
+                            uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
+                            hipStream_t st) {
+  if (sum) *sum = gg_matrix_summary{};
+  if (m == 0) return GG_OK;
+  const uint32_t s = c->s;
+  if ((uint64_t)m * s >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, "gg_ani_matrix: 2^31 sketch slots or more");
+  MatrixPrep prep;
+  const gg_status ps = matrix_prepare(c, "gg_ani_matrix", d_sk, d_lens, n, d_rows, m, &prep, st);
+  if (ps != GG_OK) return ps;
+  const uint32_t *pos_row = prep.pos_row, *pos_len = prep.pos_len, *piece = prep.piece, *piece_cnt = prep.piece_cnt;
+  const uint64_t n_entries = prep.n_entries, n_columns = prep.n_columns, column_entries = prep.column_entries;
 
   MxLaunch a{d_sk, s, m, pos_row, pos_len, piece, piece_cnt, d_common, d_total, d_ani, c->k, 0.0, nullptr, 0, nullptr};
   const dim3 grid(matrix::tile_pairs_of(matrix::tiles_of(m)));
@@ -428,6 +563,43 @@ gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_l
     sum->n_columns = n_columns;
     sum->column_entries = column_entries;
     sum->ani_rechecked = 2 * flagged;  // cells: the matrix mirrors each listed entry
+  }
+  return GG_OK;
+}
+
+// ---- the pair form ------------------------------------------
+// The product over prepared positions with the thresholded epilogue: the
+// passing pairs appended to d_out (unsorted), *d_count grown by the number
+// found, nothing written past cap.  cmin / sufmin: ensure_cmin's tables on the
+// device.  Asynchronous.
+gg_status pairs_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, const uint32_t* d_cmin,
+                              const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
+                              hipStream_t st) {
+  if (p.m < 2) return GG_OK;
+  MxPairLaunch a{};
+  a.sk = d_sk;
+  a.s = c->s;
+  a.m = p.m;
+  a.pos_row = p.pos_row;
+  a.pos_len = p.pos_len;
+  a.piece = p.piece;
+  a.piece_cnt = p.piece_cnt;
+  a.k = c->k;
+  a.count = (unsigned long long*)d_count;
+  a.cmin = d_cmin;
+  a.sufmin = d_sufmin;
+  a.tmax = 2 * c->s;
+  a.zero_passes = c->sufmin_host[0] == 0;
+  a.out = d_out;
+  a.out_cap = cap;
+  // One launch takes fewer than 2^32 threads, 2^24 workgroups of 256: the tile
+  // pairs (< 2^31: pair_limits_ok) go in slices of kPairSlice, in stream order.
+  const uint32_t tile_pairs = matrix::tile_pairs_of(matrix::tiles_of(p.m));
+  const uint32_t slice = test_pair_slice();
+  for (uint32_t base = 0; base < tile_pairs; base += std::min(slice, tile_pairs - base)) {
+    a.wg_base = base;
+    hipLaunchKernelGGL(mx_common_kernel<MxPairLaunch>, dim3(std::min(slice, tile_pairs - base)), dim3(256), 0, st, a);
+    GG_HIP(c, hipGetLastError());
   }
   return GG_OK;
 }

@@ -1030,6 +1030,26 @@ gg_status pairs_index(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, u
 
 }  // namespace
 
+gg_status pairs_tables(gg_ctx* c, float min_ani, uint32_t** d_cmin, uint32_t** d_sufmin, hipStream_t st) {
+  return ensure_cmin(c, min_ani, d_cmin, d_sufmin, st);
+}
+
+gg_status sorted_pairs_device(gg_ctx* c, const gg_pair* d_pairs, uint64_t cnt, uint32_t n, gg_pair** d_sorted,
+                              hipStream_t st) {
+  // scratch as pairs_range_to_host lays it out: keys and sorted keys [cnt] u64,
+  // positions and sorted positions [cnt] u32, the sorted pairs [cnt] x 16 B
+  uint64_t* d_kv;
+  void* d_tmp;
+  const size_t tmp_bytes = pair_sort_tmp_bytes(cnt, n);
+  GG_HIP(c, scratch_t(c, "pair_sort_kv", 5 * std::max<uint64_t>(cnt, 1), &d_kv));
+  GG_HIP(c, scratch(c, "pair_sort_tmp", std::max<size_t>(tmp_bytes, 16), &d_tmp));
+  uint32_t* d_idx = (uint32_t*)(d_kv + 2 * cnt);
+  *d_sorted = (gg_pair*)(d_kv + 3 * cnt);
+  if (cnt == 0) return GG_OK;
+  GG_HIP(c, sort_pairs_device(d_pairs, cnt, n, d_kv, d_kv + cnt, d_idx, d_idx + cnt, *d_sorted, d_tmp, tmp_bytes, st));
+  return GG_OK;
+}
+
 gg_status pairs_core(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                      uint64_t tb, uint64_t te, float min_ani, gg_pair* d_out, uint64_t cap,
                      uint64_t* d_count, hipStream_t st, uint32_t n_old) {

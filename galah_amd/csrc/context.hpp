@@ -140,6 +140,10 @@ struct gg_ctx {
   // first use), so the copies from different peers run at once
   std::vector<hipStream_t> peer_streams;
   uint64_t pair_paths[GG_PATH_COUNT] = {};  // gg_pair_paths
+  // what pairs_rows_device runs (gg_set_pairs_path), and its calls that ran
+  // the default K2, the matrix by request, the matrix by AUTO's choice
+  int pairs_path = GG_PAIRS_PATH_DEFAULT;
+  uint64_t pairs_paths_taken[3] = {};
   // of the index calls abandoned for the gate kernel (GG_PATH_INDEX_ABANDONED),
   // those whose member reads outweighed the gate kernel's merges (gg_info_line)
   uint64_t index_costly = 0;
@@ -286,12 +290,37 @@ gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32
                                    const uint32_t* d_members, const uint32_t* offsets, uint32_t n_groups,
                                    uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
                                    hipStream_t st);
-// K2 over every tile of n resident rows into context scratch (resident.cpp):
-// max(2^20, 16 n) pairs clipped to n (n - 1) / 2, the count read back, one
-// retry at the exact count.  *d_out the pairs (unsorted), *cnt their number,
-// *passes 1 or 2 (n < 2: nothing is run, 0 pairs).  Synchronises st.
+// The positions part of a matrix call (ani_matrix.hip), in context scratch
+// until the next matrix call on the context, and the counts read back.
+struct MatrixPrep {
+  const uint32_t *pos_row, *pos_len, *piece, *piece_cnt;
+  uint32_t m;
+  uint64_t n_entries, n_columns, column_entries;
+};
+gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st);
+// The pair form of the product (ani_matrix.hip, matrix_core.hpp): the passing
+// pairs of the prepared positions appended to d_out, gg_pairs_device's output
+// contract.  d_cmin / d_sufmin: pairs_tables'.  Asynchronous.
+gg_status pairs_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, const uint32_t* d_cmin,
+                              const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
+                              hipStream_t st);
+// cmin / sufmin of min_ani on the device, as every pair kernel takes them
+// (api.cpp's ensure_cmin; c->sufmin_host[0] == 0: some pair without a shared hash passes)
+gg_status pairs_tables(gg_ctx* c, float min_ani, uint32_t** d_cmin, uint32_t** d_sufmin, hipStream_t st);
+// cnt < 2^31 device pairs with row indices < n sorted by (i, j) into context
+// scratch (*d_sorted); enqueued on st
+gg_status sorted_pairs_device(gg_ctx* c, const gg_pair* d_pairs, uint64_t cnt, uint32_t n, gg_pair** d_sorted,
+                              hipStream_t st);
+// The passing pairs of n resident rows into context scratch (resident.cpp),
+// by the context's pairs path (gg_set_pairs_path): K2 over every tile, or the
+// pair form of the matrix product.  max(2^20, 16 n) pairs clipped to
+// n (n - 1) / 2, the count read back, one retry at the exact count.  *d_out
+// the pairs (unsorted), *cnt their number, *passes 1 or 2 (n < 2: nothing is
+// run, 0 pairs); msum (may be null) what ran.  Synchronises st.
 gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                            float min_ani, gg_pair** d_out, uint64_t* cnt, uint32_t* passes, hipStream_t st);
+                            float min_ani, gg_pair** d_out, uint64_t* cnt, uint32_t* passes, hipStream_t st,
+                            gg_pairs_matrix_summary* msum = nullptr);
 // Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
 // ani_f32_device, cluster_device; with sum, the partition of
 // preclusters_device.  *d_pairs / *d_ani (may be null) receive the scratch

@@ -68,7 +68,7 @@ GG_MATRIX_HD inline uint32_t column_id(uint64_t inclusive_sum) { return (uint32_
 
 // ---- tiles --------------------------------------------------------------------
 GG_MATRIX_HD inline uint32_t tiles_of(uint32_t m) { return (m + kTile - 1) / kTile; }
-GG_MATRIX_HD inline uint32_t tile_pairs_of(uint32_t tiles) { return tiles * (tiles + 1) / 2; }  // <= 131,328
+GG_MATRIX_HD inline uint32_t tile_pairs_of(uint32_t tiles) { return tiles * (tiles + 1) / 2; }  // (tiles < 2^16)
 // workgroup p -> (ti <= tj), p = tj (tj + 1) / 2 + ti
 GG_MATRIX_HD inline void tile_pair_of(uint32_t p, uint32_t* ti, uint32_t* tj) {
   uint32_t j = (uint32_t)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
@@ -127,6 +127,76 @@ GG_MATRIX_HD inline void cell_counts(bool same, Ptr A, uint32_t la, uint64_t las
     *common = common_ab;
     *total = validate::total_from_rank(lt, rank, common_ab);
   }
+}
+
+// ---- the pair form -------------------------------------------------
+// The same product with a thresholded epilogue: instead of an [m x m] matrix,
+// the list of pairs that pass gg_pairs' test (the rule of the gate kernel's
+// epilogue, pairs_gate.hip).  cmin[t] is the smallest common that passes at
+// total t (tmax = 2 s), sufmin[t] = min(cmin[t .. tmax]), zero_passes whether
+// some cmin[t] is 0, all three as ensure_cmin builds them.
+//   Cells visited.  Positions pa < pb only, in a diagonal tile as well; two
+//     positions that name the same row emit nothing (positions whose index is
+//     out of range all name the one row kNoRow, which is empty).
+//   An empty row on either side passes iff cmin[0] == 0, as (i, j, 0, 0).
+//   The candidate test, before any memory is touched: common >=
+//     sufmin[min(la, lb)].  finch's merge ends when the row that ends first
+//     is exhausted, so total >= that row's length >= min(la, lb) (not
+//     max(la, lb): {1, 2} against 100 larger hashes gives total 2), and
+//     sufmin[min(la, lb)] <= cmin[total]: no passing pair fails it.  Only a
+//     candidate pays the rank search of cell_counts.
+//   The pass test.  total <= tmax and common >= cmin[total].
+//   The early exit.  A tile pair that ran no chunk holds only zero counts;
+//     without zero_passes every cmin[t] >= 1, so nothing of it can pass.
+//   What is emitted.  (min(row_a, row_b), max(row_a, row_b), common, total):
+//     row indices of the sketch matrix, not positions.
+//   Limits.  m s < 2^31 sketch slots, fewer than 2^31 tile pairs; kMaxRows
+//     does not apply (there is no cell index).
+//   Launches.  One launch takes fewer than 2^32 threads, so fewer than 2^24
+//     workgroups of 256: the tile pairs go in slices of kPairSlice, workgroup
+//     w of the slice that begins at `base` taking tile pair base + w.
+constexpr uint32_t kPairSlice = 1u << 23;      // tile pairs of one launch (2^31 threads)
+constexpr uint32_t kPairStage = 4096;          // pairs a workgroup stages in the image area (kTile^2, 16 B each)
+static_assert(kPairStage == kTile * kTile && kPairStage * 16 <= 2 * kTileBytes, "the image area holds a tile pair's pairs");
+
+inline bool pair_limits_ok(uint64_t m, uint64_t sketch_size) {
+  const uint64_t tiles = (m + kTile - 1) / kTile;
+  return m * sketch_size < (1ull << 31) && m < (1ull << 31) && tiles * (tiles + 1) / 2 < (1ull << 31);
+}
+GG_MATRIX_HD inline bool pair_visited(uint32_t pa, uint32_t pb, uint32_t row_a, uint32_t row_b) {
+  return pa < pb && row_a != row_b;
+}
+GG_MATRIX_HD inline bool pair_early_exit(bool ran_a_chunk, bool zero_passes) { return !ran_a_chunk && !zero_passes; }
+template <typename Tab>
+GG_MATRIX_HD inline bool pair_candidate(uint32_t la, uint32_t lb, uint32_t common_ab, Tab cmin, Tab sufmin) {
+  if (la == 0 || lb == 0) return cmin[0] == 0;
+  return common_ab >= sufmin[la < lb ? la : lb];
+}
+template <typename Tab>
+GG_MATRIX_HD inline bool pair_passes(uint32_t common, uint32_t total, Tab cmin, uint32_t tmax) {
+  return total <= tmax && common >= cmin[total];
+}
+// One visited cell (pair_visited holds): whether it passes, and its counts.
+// A / B, la / lb, last_a / last_b and common_ab as cell_counts takes them.
+template <typename Ptr, typename Tab>
+GG_MATRIX_HD inline bool pair_cell(Ptr A, uint32_t la, uint64_t last_a, Ptr B, uint32_t lb, uint64_t last_b,
+                                   uint32_t common_ab, Tab cmin, Tab sufmin, uint32_t tmax, uint32_t* common,
+                                   uint32_t* total) {
+  *common = *total = 0;
+  if (!pair_candidate(la, lb, common_ab, cmin, sufmin)) return false;
+  if (la == 0 || lb == 0) return true;  // finch: common 0, total 0
+  cell_counts(false, A, la, last_a, B, lb, last_b, common_ab, common, total);
+  return pair_passes(*common, *total, cmin, tmax);
+}
+// The upper bound of the product's work and the lower bound of the inverted
+// index's member reads (sum of g^2 over the columns >= column_entries^2 /
+// n_columns, Cauchy-Schwarz), from the counts the call reads back anyway.
+inline uint64_t pair_chunk_rounds(uint64_t m, uint64_t n_columns) {
+  const uint64_t tiles = (m + kTile - 1) / kTile;
+  return tiles * (tiles + 1) / 2 * ((n_columns + kChunk - 1) / kChunk);
+}
+inline uint64_t pair_index_reads(uint64_t n_columns, uint64_t column_entries) {
+  return n_columns ? column_entries * column_entries / n_columns : 0;  // (column_entries < 2^31)
 }
 
 // ---- the columns on the host ------------------------------------------------------

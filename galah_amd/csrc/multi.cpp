@@ -1173,6 +1173,89 @@ gg_status gg_cluster_files_resident(gg_ctx* ctx, const char* const* paths, uint3
   return GG_OK;
 }
 
+gg_status gg_precluster_files_resident(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                       const char* cache_dir, gg_pair** pairs, float** ani, uint64_t* n_out,
+                                       gg_pairs_matrix_summary* summary) {
+  const char* who = "gg_precluster_files_resident";
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  if (summary) *summary = gg_pairs_matrix_summary{};
+  if (!pairs || !ani || !n_out || (n_paths && !paths))
+    return fail(ctx, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  if (std::isnan(min_ani)) return fail(ctx, GG_ERR_INVALID_ARG, std::string(who) + ": min_ani is NaN");
+  *pairs = nullptr;
+  *ani = nullptr;
+  *n_out = 0;
+  for (double& x : ctx->phase_ms) x = 0.0;
+  const std::vector<gg_ctx*> ms = members(ctx);
+  gg_ctx* m = ms[0];
+  const uint32_t n = n_paths, s = m->s;
+  std::vector<Rows> rows;
+  std::vector<RowSpan> spans;
+  // a multi-device context sketches on every member; the rows then go to the first through the host
+  std::vector<uint64_t> h_sk;
+  std::vector<uint32_t> h_len;
+  if (ms.size() > 1) {
+    h_sk.resize((size_t)std::max(n, 1u) * s);
+    h_len.resize(std::max(n, 1u));
+  }
+  auto t0 = Clock::now();
+  // (every file is read and sketched, even a lone one: gg_precluster_files_cached)
+  gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, ms.size() > 1 ? h_sk.data() : nullptr,
+                                      ms.size() > 1 ? h_len.data() : nullptr, nullptr);
+  if (st != GG_OK) return st;
+  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
+  t0 = Clock::now();
+  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+  auto run = [&]() -> gg_status {
+    const uint64_t* d_sk = n ? rows[0].sk : nullptr;
+    const uint32_t* d_len = n ? rows[0].len : nullptr;
+    if (n && ms.size() > 1) {
+      uint64_t* up_sk;
+      uint32_t* up_len;
+      GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)n * s, &up_sk));
+      GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)n, &up_len));
+      GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+      GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+      d_sk = up_sk;
+      d_len = up_len;
+    }
+    // the pairs by the context's path, sorted by (i, j), and their f32 ANI, all on the resident rows
+    gg_pair *d_pairs = nullptr, *d_sorted = nullptr;
+    float* d_val = nullptr;
+    uint64_t cnt = 0;
+    uint32_t passes = 0;
+    gg_status r = pairs_rows_device(m, who, d_sk, d_len, n, min_ani, &d_pairs, &cnt, &passes, m->stream, summary);
+    if (r != GG_OK) return r;
+    r = sorted_pairs_device(m, d_pairs, cnt, n, &d_sorted, m->stream);
+    if (r != GG_OK) return r;
+    GG_HIP(m, scratch_t(m, "rs_ani", (size_t)std::max<uint64_t>(cnt, 1), &d_val));
+    r = ani_f32_device(m, d_sorted, cnt, d_val, nullptr, nullptr, m->stream);
+    if (r != GG_OK) return r;
+    *pairs = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
+    *ani = (float*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(float));
+    if (!*pairs || !*ani) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+    if (cnt) {
+      GG_HIP(m, hipMemcpyAsync(*pairs, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, m->stream));
+      GG_HIP(m, hipMemcpyAsync(*ani, d_val, cnt * sizeof(float), hipMemcpyDeviceToHost, m->stream));
+    }
+    GG_HIP(m, hipStreamSynchronize(m->stream));
+    *n_out = cnt;
+    return GG_OK;
+  };
+  st = run();
+  ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
+  if (st != GG_OK) {
+    free(*pairs);
+    free(*ani);
+    *pairs = nullptr;
+    *ani = nullptr;
+    *n_out = 0;
+    if (summary) *summary = gg_pairs_matrix_summary{};
+    if (m != ctx) ctx->err = m->err;
+  }
+  return st;
+}
+
 gg_status gg_precluster_matrices_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
                                        const char* cache_dir, uint32_t** members, uint32_t** offsets,
                                        uint32_t* n_groups, uint64_t** cell_offsets, uint32_t** common,

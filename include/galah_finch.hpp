@@ -127,8 +127,10 @@ inline std::string rust_f64(double x) {
 
 namespace detail {
 // sketch + all pairs + threshold on an existing context; takes ownership of ctx
+// pairs_path >= 0 (GG_PAIRS_PATH_*): the resident call under that path, on a
+// one-device context and below debug level; the result is the same
 inline SortedPairGenomeDistanceCache distances_on(gg_ctx* ctx, const std::vector<std::string>& paths, float min_ani,
-                                                  int kmer_length) {
+                                                  int kmer_length, int pairs_path = -1) {
   if (!ctx)
     throw std::runtime_error(std::string("Failed to sketch genomes with finch: ") + gg_thread_last_error());
   gg_set_host_threads(ctx, current_num_threads());
@@ -152,11 +154,18 @@ inline SortedPairGenomeDistanceCache distances_on(gg_ctx* ctx, const std::vector
       return 0;
     }
   } each{&paths, kmer_length};
-  const gg_status st = debug_sink()
-                           ? gg_precluster_files_each(ctx, c_paths.data(), (uint32_t)c_paths.size(), min_ani, nullptr,
-                                                      &Each::sink, &each, &pairs, &ani, &n, nullptr)
-                           : gg_precluster_files(ctx, c_paths.data(), (uint32_t)c_paths.size(), min_ani, &pairs, &ani,
-                                                 &n);
+  const bool resident = !debug_sink() && pairs_path >= 0 && gg_device_count(ctx) == 1;
+  gg_status st = resident ? gg_set_pairs_path(ctx, pairs_path) : GG_OK;  // (an unknown path is an error)
+  if (st == GG_OK) {
+    if (debug_sink())
+      st = gg_precluster_files_each(ctx, c_paths.data(), (uint32_t)c_paths.size(), min_ani, nullptr, &Each::sink, &each,
+                                    &pairs, &ani, &n, nullptr);
+    else if (resident)
+      st = gg_precluster_files_resident(ctx, c_paths.data(), (uint32_t)c_paths.size(), min_ani, nullptr, &pairs, &ani,
+                                        &n, nullptr);
+    else
+      st = gg_precluster_files(ctx, c_paths.data(), (uint32_t)c_paths.size(), min_ani, &pairs, &ani, &n);
+  }
   if (st != GG_OK) {
     std::string msg = gg_last_error(ctx);
     gg_destroy(ctx);
@@ -201,19 +210,28 @@ inline SortedPairGenomeDistanceCache finch_distances_on(const std::vector<int>& 
       min_ani, kmer_length);
 }
 
-// src/finch.rs:4-24
+// src/finch.rs:4-24.  pairs_path: -1 (the default K2 through the calls used so
+// far) or GG_PAIRS_PATH_DEFAULT / _MATRIX / _AUTO: distances() and
+// galah::cluster then take the resident calls under that pairs path
+// (gg_set_pairs_path; MATRIX suits thousands of strains of one species).  The
+// results do not depend on it; it is ignored on a multi-device context and,
+// in distances(), when a debug sink is set (every compared pair is logged).
 class FinchPreclusterer : public PreclusterDistanceFinder {
  public:
-  FinchPreclusterer(float min_ani, size_t num_kmers = 1000, uint8_t kmer_length = 21)
-      : min_ani(min_ani), num_kmers(num_kmers), kmer_length(kmer_length) {}
+  FinchPreclusterer(float min_ani, size_t num_kmers = 1000, uint8_t kmer_length = 21, int pairs_path = -1)
+      : min_ani(min_ani), num_kmers(num_kmers), kmer_length(kmer_length), pairs_path(pairs_path) {}
   SortedPairGenomeDistanceCache distances(const std::vector<std::string>& paths) override {
-    return finch_distances(paths, min_ani, num_kmers, kmer_length);
+    if (pairs_path < 0) return finch_distances(paths, min_ani, num_kmers, kmer_length);
+    gg_status st = GG_OK;
+    return detail::distances_on(gg_create_multi(kmer_length, (uint32_t)num_kmers, 0, nullptr, 0, &st), paths, min_ani,
+                                kmer_length, pairs_path);
   }
   const char* method_name() const override { return "finch"; }
 
   float min_ani;  // fraction, not percentage
   size_t num_kmers;
   uint8_t kmer_length;
+  int pairs_path;
 };
 
 // src/lib.rs:29-37
@@ -285,8 +303,15 @@ inline std::vector<std::vector<size_t>> cluster(const std::vector<std::string>& 
   const uint32_t n = (uint32_t)genomes.size();
   std::vector<uint32_t> rep_of(n), members(n), offsets((size_t)n + 1);
   info("Sketching MinHash representations of each genome with finch ..");  // src/finch.rs:46
-  st = gg_cluster_files(ctx, c_paths.data(), n, finch->min_ani, clusterer.get_ani_threshold(), nullptr, rep_of.data(),
-                        nullptr, nullptr, nullptr);
+  if (finch->pairs_path >= 0 && gg_device_count(ctx) == 1) {  // the resident call under the preclusterer's path
+    st = gg_set_pairs_path(ctx, finch->pairs_path);
+    if (st == GG_OK)
+      st = gg_cluster_files_resident(ctx, c_paths.data(), n, finch->min_ani, clusterer.get_ani_threshold(), nullptr,
+                                     rep_of.data(), nullptr);
+  } else {
+    st = gg_cluster_files(ctx, c_paths.data(), n, finch->min_ani, clusterer.get_ani_threshold(), nullptr,
+                          rep_of.data(), nullptr, nullptr, nullptr);
+  }
   if (st != GG_OK) {
     const std::string msg = gg_last_error(ctx);
     gg_destroy(ctx);
@@ -459,6 +484,30 @@ inline std::vector<float> ani_matrix(const std::vector<std::string>& paths, size
   const std::string msg = st != GG_OK ? gg_last_error(ctx) : "";
   gg_destroy(ctx);
   if (st != GG_OK) throw std::runtime_error("Failed to sketch genomes with finch: " + msg);  // src/finch.rs:50
+  return out;
+}
+
+// The pairs of a sketch matrix at or above min_ani (a fraction), sorted by
+// (i, j), by the matrix product with the thresholded epilogue
+// (gg_pairs_matrix): gg_pairs' answer, built for dense sets.  sketches is
+// [lens.size() x sketch_size], rows ascending; rows (may be null: every row)
+// lists the rows to compare, none twice.
+inline std::vector<gg_pair> pairs_matrix(const std::vector<uint64_t>& sketches, const std::vector<uint32_t>& lens,
+                                         size_t sketch_size, float min_ani, const std::vector<uint32_t>* rows = nullptr,
+                                         uint8_t kmer_length = 21, gg_pairs_matrix_summary* summary = nullptr) {
+  if (sketches.size() != lens.size() * sketch_size) throw std::invalid_argument("sketches must be [n x sketch_size]");
+  gg_status st = GG_OK;
+  gg_ctx* ctx = gg_create_multi(kmer_length, (uint32_t)sketch_size, 0, nullptr, 0, &st);
+  if (!ctx) throw std::runtime_error(gg_thread_last_error());
+  gg_pair* p = nullptr;
+  uint64_t n = 0;
+  st = gg_pairs_matrix(ctx, sketches.data(), lens.data(), (uint32_t)lens.size(), rows ? rows->data() : nullptr,
+                       (uint32_t)(rows ? rows->size() : lens.size()), min_ani, &p, &n, summary);
+  const std::string msg = st != GG_OK ? gg_last_error(ctx) : "";
+  gg_destroy(ctx);
+  if (st != GG_OK) throw std::runtime_error(msg);
+  std::vector<gg_pair> out(p, p + n);
+  gg_free(p);
   return out;
 }
 

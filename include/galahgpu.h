@@ -667,6 +667,82 @@ gg_status gg_precluster_matrices_files(gg_ctx* ctx, const char* const* paths, ui
                                        uint32_t* n_groups, uint64_t** cell_offsets, uint32_t** common,
                                        uint32_t** total, float** ani, gg_matrix_summary* summary);
 
+/* ---- passing pairs from the matrix product -------------- */
+/* gg_pairs' answer by the other way to common(i, j): the product A A^T of
+ * the sections above with a thresholded epilogue, which emits the pairs at or
+ * above min_ani instead of an [m x m] matrix.  Built for dense sets --
+ * thousands of strains of one species -- where the inverted index pays g^2
+ * member reads per hash shared by g rows.  There is no dense output and no
+ * 32768-row cap: one call takes m rows with m * sketch size < 2^31 and fewer
+ * than 2^31 64 x 64 tile pairs, else GG_ERR_INVALID_ARG before any row is
+ * read (2,147,483 rows at sketch size 1000; 4,194,240 rows at 512 or less;
+ * the tile pairs go to the device in as many launches as they need).  Pairs are (i < j) row indices of the sketch matrix with finch's merge
+ * counts, exactly gg_pairs' records.  These kernels have no gg_timing_read
+ * slot. */
+enum { GG_PAIRS_PATH_DEFAULT = 0, GG_PAIRS_PATH_MATRIX = 1, GG_PAIRS_PATH_AUTO = 2 };
+
+typedef struct gg_pairs_matrix_summary {
+  uint64_t n_entries;     /* these three as gg_matrix_summary */
+  uint64_t n_columns;
+  uint64_t column_entries;
+  uint64_t n_pairs;       /* passing pairs found (device form: may exceed out_cap) */
+  uint64_t chunk_rounds;  /* tile pairs x ceil(n_columns / 512): upper bound of the product's work */
+  uint64_t index_reads;   /* column_entries^2 / n_columns (0 without columns): lower bound of the
+                             inverted index's member reads, sum of g^2 over the columns */
+  uint32_t path;          /* GG_PAIRS_PATH_MATRIX or GG_PAIRS_PATH_DEFAULT: what produced the pairs */
+  uint32_t pair_passes;   /* 1, or 2 after the capacity retry */
+} gg_pairs_matrix_summary;
+
+/* Device-resident, gg_pairs_device's output contract: the passing pairs among
+ * the m listed rows (d_rows NULL: rows 0..m-1) are appended to d_out unsorted,
+ * *d_count (device u64) grows by the number found, entries past out_cap are
+ * dropped and nothing is written past out_cap.  Synchronises the stream: one
+ * read-back before the product, as gg_ani_matrix_device (and, with a summary,
+ * one of *d_count after it).  d_rows is not checked: an index >= n is an empty
+ * row (emitted, when min_ani lets empty rows pass, with the index 0xFFFFFFFF;
+ * all such positions count as one row), and a row listed twice gets its pairs
+ * once per position, none with itself.  summary may be NULL. */
+gg_status gg_pairs_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                 const uint32_t* d_rows, uint32_t m, float min_ani, gg_pair* d_out,
+                                 uint64_t out_cap, uint64_t* d_count, gg_pairs_matrix_summary* summary,
+                                 void* stream);
+/* Host arrays in; *out library-owned (gg_free), sorted by (i, j), as gg_pairs
+ * gives it over the listed rows.  GG_ERR_INVALID_ARG for an index >= n, an
+ * index listed twice, lens[g] > sketch_size, NaN min_ani or the limits above
+ * (taken of n as well: every row is uploaded).  The first output capacity is
+ * min(m (m - 1) / 2, max(2^20, 16 m)) pairs, with one retry at the exact
+ * count.  A multi-device context acts on its first member. */
+gg_status gg_pairs_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                          const uint32_t* rows, uint32_t m, float min_ani, gg_pair** out, uint64_t* n_out,
+                          gg_pairs_matrix_summary* summary);
+/* What produces the pairs inside gg_cluster_rows_device,
+ * gg_cluster_files_resident, gg_precluster_matrices_files and
+ * gg_precluster_files_resident.  DEFAULT (a new context's): K2 as ever.
+ * MATRIX: the pair form over all rows (GG_ERR_INVALID_ARG from those calls
+ * when the limits do not hold).  AUTO: the positions part of the matrix call
+ * is run and its three counts read back; the product is taken iff there is a
+ * column, the limits hold and index_reads > R * chunk_rounds (R:
+ * GALAHGPU_PAIRS_MATRIX_RATIO), else K2 exactly as DEFAULT.
+ * AUTO pays the 64-bit sort of n * sketch size slots (about 0.9 ms per 10^7)
+ * even when it then runs K2, which is why it is not the default.  The results
+ * do not depend on the path.  An unknown value is GG_ERR_INVALID_ARG.  A
+ * multi-device context sets its first member, which runs these calls. */
+gg_status gg_set_pairs_path(gg_ctx* ctx, int path);
+/* The path set (a null context: -1). */
+int gg_pairs_path(const gg_ctx* ctx);
+/* Calls of the above since creation that ran the default K2, the matrix by
+ * request, and the matrix by AUTO's choice. */
+gg_status gg_pairs_paths_taken(const gg_ctx* ctx, uint64_t* counts /* [3] */);
+/* gg_precluster_files_cached with the rows resident on the (first) device:
+ * the pairs by the context's path, sorted by (i, j) on the device,
+ * gg_ani_f32_device over them, and only pairs and ANI copied back.  The
+ * outputs equal gg_precluster_files_cached's whatever the path.  summary (may
+ * be NULL) reports what ran; under DEFAULT its column counts are 0 (under AUTO
+ * they are filled even when K2 ran). */
+gg_status gg_precluster_files_resident(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                       const char* cache_dir, gg_pair** pairs, float** ani, uint64_t* n_out,
+                                       gg_pairs_matrix_summary* summary);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);

@@ -182,6 +182,26 @@ pub struct gg_matrix_summary {
     pub ani_rechecked: u64,
 }
 
+/// What produces the pairs of resident rows (`gg_set_pairs_path`).
+pub const GG_PAIRS_PATH_DEFAULT: c_int = 0;
+pub const GG_PAIRS_PATH_MATRIX: c_int = 1;
+pub const GG_PAIRS_PATH_AUTO: c_int = 2;
+
+/// What `gg_pairs_matrix*` / `gg_precluster_files_resident` report beside the
+/// pairs (`gg_pairs_matrix_summary`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gg_pairs_matrix_summary {
+    pub n_entries: u64,
+    pub n_columns: u64,
+    pub column_entries: u64,
+    pub n_pairs: u64,
+    pub chunk_rounds: u64,
+    pub index_reads: u64,
+    pub path: u32,
+    pub pair_passes: u32,
+}
+
 /// `gg_pair_sink`: a block of compared pairs; return 0 to go on.
 pub type gg_pair_sink = Option<unsafe extern "C" fn(user: *mut c_void, pairs: *const gg_pair, n: u64) -> c_int>;
 
@@ -360,6 +380,21 @@ extern "C" {
                                         n_groups: *mut u32, cell_offsets: *mut *mut u64, common: *mut *mut u32,
                                         total: *mut *mut u32, ani: *mut *mut f32, summary: *mut gg_matrix_summary)
         -> GgStatus;
+
+    // passing pairs from the matrix product
+    pub fn gg_pairs_matrix_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32,
+                                  d_rows: *const u32, m: u32, min_ani: f32, d_out: *mut gg_pair, out_cap: u64,
+                                  d_count: *mut u64, summary: *mut gg_pairs_matrix_summary, stream: *mut c_void)
+        -> GgStatus;
+    pub fn gg_pairs_matrix(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, rows: *const u32,
+                           m: u32, min_ani: f32, out: *mut *mut gg_pair, n_out: *mut u64,
+                           summary: *mut gg_pairs_matrix_summary) -> GgStatus;
+    pub fn gg_set_pairs_path(ctx: *mut gg_ctx, path: c_int) -> GgStatus;
+    pub fn gg_pairs_path(ctx: *const gg_ctx) -> c_int;
+    pub fn gg_pairs_paths_taken(ctx: *const gg_ctx, counts: *mut u64) -> GgStatus;
+    pub fn gg_precluster_files_resident(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
+                                        cache_dir: *const c_char, pairs: *mut *mut gg_pair, ani: *mut *mut f32,
+                                        n_out: *mut u64, summary: *mut gg_pairs_matrix_summary) -> GgStatus;
 
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;
