@@ -25,7 +25,10 @@ K1_BLOCK = 256  # kBlock of sketch.hip
 
 
 def seg_len(k):
-    """k1_seg_len(k, 4) of gg_internal.hpp (44 at k = 21)."""
+    """k1_seg_len(k, 4) of gg_internal.hpp: the k-mers of a 64-base window,
+    65 - k, rounded down to a multiple of the tau-branch group of 4 and capped
+    at 48.  48 for k <= 17, 44 for k = 18..21, 40 for 22..25, 36 for 26..29,
+    32 for 30..32."""
     return min((65 - k) // 4 * 4, 48)
 
 
@@ -118,10 +121,20 @@ def test_funnel_offsets_at_buffer_end(off):
     check([genome])
 
 
-@pytest.mark.parametrize("k,s,seed", [(k, s, 0) for k in (5, 16, 31, 32) for s in (50, 500)] + [(16, 500, 12345)])
+OTHER_K = ([(k, 500, 0) for k in range(1, 33) if k != 21] + [(k, 50, 0) for k in (5, 16, 31, 32)] +
+           [(16, 500, 12345), (22, 500, 12345)])
+
+
+@pytest.mark.parametrize("k,s,seed", OTHER_K)
 def test_other_k(k, s, seed):
-    """L = 48, 48, 32, 32 at k = 5, 16, 31, 32; one case with a non-zero seed
-    (the kernel variant that keeps the seed terms)."""
+    """Every k the kernel is compiled for but 21 (the tests above).  The
+    segment is L = min(4 * ((65 - k) // 4), 48) k-mers: 48 up to k = 17, 44 at
+    k = 18..21, 40 at 22..25, 36 at 26..29 and 32 at 30..32, and the k-mer's
+    place in the lane's window takes another shift branch of window64 at every
+    k.  Below k = 5 a genome holds fewer distinct k-mers than s, so tau climbs
+    to 2^64 - 1.  Two cases with a non-zero seed (the kernel variant that keeps
+    the seed terms): k = 16, one murmur block and no tail, and k = 22, a block
+    and a tail of two group tables."""
     with ga.Context(k=k, sketch_size=s, seed=seed) as ctx:
         check(list(edge_genomes(k)), k, s, seed, ctx=ctx)
         check(list(crossing_genomes(k)), k, s, seed, ctx=ctx)
