@@ -72,7 +72,8 @@ EXPORTED_SYMBOLS = (
     "gg_ani_matrix_host", "gg_ani_matrix", "gg_ani_matrix_device", "gg_ani_matrix_files",
     "gg_ani_matrix_group_cells", "gg_ani_matrix_groups_host", "gg_ani_matrix_groups", "gg_ani_matrix_groups_device",
     "gg_precluster_matrices_files",
-    "gg_pairs_matrix_device", "gg_pairs_matrix", "gg_set_pairs_path", "gg_pairs_path", "gg_pairs_paths_taken",
+    "gg_pairs_matrix_device", "gg_pairs_matrix", "gg_pairs_border_matrix_device", "gg_pairs_border_matrix",
+    "gg_set_pairs_path", "gg_pairs_path", "gg_pairs_paths_taken",
     "gg_precluster_files_resident",
 )
 
@@ -260,6 +261,10 @@ _sig("gg_pairs_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, ctypes.c_f
                                       ctypes.POINTER(_PairsMatrixSummary), _vp])
 _sig("gg_pairs_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp),
                                ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
+_sig("gg_pairs_border_matrix_device", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, _vp, _u64, _vp,
+                                              ctypes.POINTER(_PairsMatrixSummary), _vp])
+_sig("gg_pairs_border_matrix", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, ctypes.POINTER(_vp),
+                                       ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
 _sig("gg_set_pairs_path", _i32, [_vp, _i32])
 _sig("gg_pairs_path", _i32, [_vp])
 _sig("gg_pairs_paths_taken", _i32, [_vp, _vp])
@@ -1190,12 +1195,28 @@ class Context:
             raise self._err(st)
         return _take_pairs(outp, cnt.value), summary.as_dict()
 
+    def pairs_border_matrix(self, sketches, lens, n_old, min_ani):
+        """pairs_border() by the border form of the matrix product
+        (gg_pairs_border_matrix): for new strains added to a
+        dense set -> (pairs sorted by (i, j), summary dict of
+        gg_pairs_matrix_summary; its column counts are the border's)."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        outp, cnt = _vp(), _u64()
+        summary = _PairsMatrixSummary()
+        st = _L.gg_pairs_border_matrix(self._c, _ptr(sk), _ptr(ln), n, int(n_old), ctypes.c_float(min_ani),
+                                       ctypes.byref(outp), ctypes.byref(cnt), ctypes.byref(summary))
+        if st != GG_OK:
+            raise self._err(st)
+        return _take_pairs(outp, cnt.value), summary.as_dict()
+
     def set_pairs_path(self, path):
         """What produces the pairs inside cluster_rows_device,
-        cluster_files_resident, precluster_matrices_files and
-        precluster_files_resident: "default" (K2), "matrix" (the pair form of
-        the matrix product) or "auto" (the product when the index is certainly
-        the dearer, gg_set_pairs_path) -> the path that was set before."""
+        cluster_files_resident, precluster_matrices_files,
+        precluster_files_resident and the border calls pairs_border,
+        pairs_border_device and update_files: "default" (K2), "matrix" (the
+        pair form of the matrix product, for a border its border form) or
+        "auto" (the product when the index is certainly the dearer,
+        gg_set_pairs_path) -> the path that was set before."""
         if path not in PAIRS_PATHS:
             raise ValueError("pairs path must be one of %s, not %r" % (", ".join(PAIRS_PATHS), path))
         before = self.pairs_path
@@ -1561,6 +1582,23 @@ class Context:
             raise self._err(st)
         return summary.as_dict() if want_summary else None
 
+    def pairs_border_matrix_device(self, d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count,
+                                   want_summary=True, stream=None):
+        """pairs_border_matrix over device-resident tensors, the output
+        contract of pairs_border_device: the border's passing pairs appended
+        unsorted to d_out, d_count (u64) grown by the number found, nothing
+        written past out_cap; n_old == n runs nothing.  Synchronises the
+        stream -> summary dict (None without want_summary; n_pairs may exceed
+        out_cap)."""
+        summary = _PairsMatrixSummary()
+        st = _L.gg_pairs_border_matrix_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, int(n_old),
+                                              ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
+                                              ctypes.byref(summary) if want_summary else None,
+                                              None if stream is None else stream)
+        if st != GG_OK:
+            raise self._err(st)
+        return summary.as_dict() if want_summary else None
+
     def ani_matrix_device(self, d_sketches, d_lens, n, d_rows, m, d_common=None, d_total=None, d_ani=None,
                           stream=None):
         """ani_matrix over device-resident tensors: d_sketches [n, s] u64,
@@ -1806,7 +1844,9 @@ class FinchPreclusterer(PreclusterDistanceFinder):
         """pairs_path: None (the default K2 through the calls used so far),
         or "default" / "matrix" / "auto": distances() and cluster() then run
         the resident calls under that pairs path (Context.set_pairs_path;
-        "matrix" suits thousands of strains of one species).  The results do
+        "matrix" suits thousands of strains of one species), and update()
+        (so distances_state() and cluster_update()) evaluates its border
+        under it.  The results do
         not depend on it.  It is ignored on a multi-device context and, in
         distances(), at debug level (see distances).  The path is set on the
         shared cached context around the call and put back after it: two
@@ -1859,8 +1899,17 @@ class FinchPreclusterer(PreclusterDistanceFinder):
             seen.add(p)
         try:
             ctx = _context(self.kmer_length, self.num_kmers)
-            sk, lens, border, border_ani = ctx.update_files(state.sketches, state.lens, new_paths,
-                                                            float(self.min_ani), cache_dir=self.sketch_cache_dir)
+            if self.pairs_path is None or ctx.device_count != 1:
+                sk, lens, border, border_ani = ctx.update_files(state.sketches, state.lens, new_paths,
+                                                                float(self.min_ani), cache_dir=self.sketch_cache_dir)
+            else:
+                before = ctx.set_pairs_path(self.pairs_path)  # (the cached context is shared: put back what was set)
+                try:
+                    sk, lens, border, border_ani = ctx.update_files(state.sketches, state.lens, new_paths,
+                                                                    float(self.min_ani),
+                                                                    cache_dir=self.sketch_cache_dir)
+                finally:
+                    ctx.set_pairs_path(before)
         except GalahGpuError as e:
             raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
         pairs = np.concatenate([state.pairs, border])

@@ -52,6 +52,15 @@
 // add per workgroup and 16-byte stores.  matrix_prepare is the positions part
 // shared by the dense and the pair form; beyond kMaxRows rows (the pair form
 // only) the offsets come from mxp_positions_kernel and a scan.
+//
+// The border form is the fourth instantiation, on
+// MxBorderLaunch: the pair form over rows of which the last n_new are new,
+// with the new rows at the first positions (mxb_rows_kernel writes the map as
+// a row list), the tile pairs that hold a new tile only, the cells of a new
+// position only, and the border column rule in the positions part:
+// mxb_starts_kernel and an inclusive max give every sorted entry the first
+// entry of its run of equal hashes, mxb_flags_kernel / mxb_ids_kernel keep the
+// runs whose first entry lies at a new position.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -183,6 +192,52 @@ __global__ __launch_bounds__(256) void mx_ids_kernel(const uint64_t* __restrict_
     id_of[slot_of[i]] = matrix::in_column(K, i, ne) ? matrix::column_id(sums[i]) : kNoColumn;
 }
 
+// ---- the border column rule (matrix_core.hpp, the border form) -----------------
+// the border's positions as a row list: the new rows first
+__global__ __launch_bounds__(256) void mxb_rows_kernel(uint32_t n, uint32_t n_old, uint32_t* __restrict__ rows) {
+  for (uint32_t a = blockIdx.x * 256 + threadIdx.x; a < n; a += gridDim.x * 256)
+    rows[a] = matrix::border_row_of(a, n, n_old);
+}
+
+// start1[i] = i + 1 at the first entry of a run of equal hashes, else 0: the
+// inclusive max over it gives every entry its run's first entry (plus one)
+__global__ __launch_bounds__(256) void mxb_starts_kernel(const uint64_t* __restrict__ K, uint32_t N,
+                                                         const uint32_t* __restrict__ pos_off, uint32_t m,
+                                                         uint32_t* __restrict__ start1) {
+  const uint32_t ne = pos_off[m];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
+    start1[i] = i < ne && (i == 0 || K[i] != K[i - 1]) ? i + 1 : 0u;
+}
+
+// the run of entry i < ne is a border column's: its first entry (the lowest
+// slot of the run) lies at a new position (start1[i] >= 1: entry 0 opens a run)
+__device__ __forceinline__ bool mxb_kept(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ start1,
+                                         uint32_t i, uint32_t s, uint32_t n_new) {
+  return matrix::border_column_kept(slot_of[start1[i] - 1] / s, n_new);
+}
+
+__global__ __launch_bounds__(256) void mxb_flags_kernel(const uint64_t* __restrict__ K,
+                                                        const uint32_t* __restrict__ slot_of,
+                                                        const uint32_t* __restrict__ start1, uint32_t N,
+                                                        const uint32_t* __restrict__ pos_off, uint32_t m, uint32_t s,
+                                                        uint32_t n_new, uint64_t* __restrict__ flags) {
+  const uint32_t ne = pos_off[m];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
+    flags[i] = i < ne && mxb_kept(slot_of, start1, i, s, n_new) ? matrix::column_flags(K, i, ne) : 0ull;
+}
+
+__global__ __launch_bounds__(256) void mxb_ids_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ slot_of,
+                                                      const uint32_t* __restrict__ start1,
+                                                      const uint64_t* __restrict__ sums,
+                                                      const uint32_t* __restrict__ pos_off, uint32_t m, uint32_t s,
+                                                      uint32_t n_new, uint32_t* __restrict__ id_of) {
+  const uint32_t ne = pos_off[m];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256)
+    id_of[slot_of[i]] = matrix::in_column(K, i, ne) && mxb_kept(slot_of, start1, i, s, n_new)
+                            ? matrix::column_id(sums[i])
+                            : kNoColumn;
+}
+
 // piece[a * s ..) the ids of position a's entries that lie in a column, in the row's order; piece_cnt[a]
 __global__ __launch_bounds__(256) void mx_pieces_kernel(const uint32_t* __restrict__ id_of,
                                                         const uint32_t* __restrict__ pos_len, uint32_t s,
@@ -225,6 +280,7 @@ struct MxLaunch {
   unsigned long long* count;
   static constexpr bool kGroups = false;
   static constexpr bool kPairs = false;
+  static constexpr bool kBorder = false;
 };
 // the grouped form (matrix_core.hpp, groups): m is not read, a workgroup finds its group in tp_off
 struct MxGroupLaunch : MxLaunch {
@@ -245,6 +301,14 @@ struct MxPairLaunch : MxLaunch {
   uint64_t out_cap;
   uint32_t wg_base;  // the tile pair of the launch's workgroup 0 (a call is launched in slices)
   static constexpr bool kPairs = true;
+};
+// the border form (matrix_core.hpp, the border form): m rows at the border's
+// positions, the first n_new of them new (tiles_new tiles of them); wg_base
+// counts border tile pairs
+struct MxBorderLaunch : MxPairLaunch {
+  uint32_t n_new;
+  uint32_t tiles_new;
+  static constexpr bool kBorder = true;
 };
 
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
@@ -272,6 +336,8 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
     m = a.offsets[g + 1] - p0;
     c0 = a.cell_off[g];
     matrix::tile_pair_of(blockIdx.x - a.tp_off[g], &ti, &tj);
+  } else if constexpr (L::kBorder) {
+    matrix::border_tile_pair_of(a.wg_base + blockIdx.x, a.tiles_new, &ti, &tj);  // (< 2^31: border_limits_ok)
   } else if constexpr (L::kPairs) {
     matrix::tile_pair_of(a.wg_base + blockIdx.x, &ti, &tj);  // (< 2^31: pair_limits_ok)
   } else {
@@ -377,7 +443,10 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
         if (pa < m && pb < m) {
           ga = s_row[ra];
           gb = s_row[sb + rb];
-          if (matrix::pair_visited(pa, pb, ga, gb))
+          bool visited;
+          if constexpr (L::kBorder) visited = matrix::border_visited(pa, pb, a.n_new, ga, gb);
+          else visited = matrix::pair_visited(pa, pb, ga, gb);
+          if (visited)
             pass = matrix::pair_cell(a.sk + (uint64_t)ga * a.s, s_len[ra], s_last[ra], a.sk + (uint64_t)gb * a.s,
                                      s_len[sb + rb], s_last[sb + rb], (uint32_t)acc[nb][reg], a.cmin, a.sufmin, a.tmax,
                                      &common, &total);
@@ -456,10 +525,15 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
 // pos_row / pos_len / piece / piece_cnt in context scratch and the three counts.
 // m s < 2^31 (the caller's check).  m <= kMaxRows: mx_offsets_kernel; more rows
 // (the pair form only): mxp_positions_kernel and a scan.  Synchronises st.
+// border_n_old != kNoBorder: the border form of m == n rows -- d_rows is not
+// read, the positions are the border's, the columns by the border column rule,
+// and new_entries is counted; every other caller takes the path it took before.
 gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st) {
+                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st, uint32_t border_n_old) {
   const uint32_t s = c->s;
   const uint32_t N = (uint32_t)((uint64_t)m * s);
+  const bool border = border_n_old != kNoBorder;
+  const uint32_t n_new = border ? n - border_n_old : 0u;  // (border: m == n >= border_n_old, the caller's check)
   uint32_t *pos_row, *pos_len, *pos_off, *vals_in, *vals_out, *piece, *piece_cnt;
   uint64_t *keys_in, *keys_out, *sums, *h_back;
   GG_HIP(c, scratch_t(c, "mx_pos", (size_t)4 * m + 1, &pos_row));
@@ -472,19 +546,32 @@ gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const
   GG_HIP(c, scratch_t(c, "mx_vals_in", (size_t)N, &vals_in));
   GG_HIP(c, scratch_t(c, "mx_vals_out", (size_t)N, &vals_out));
   GG_HIP(c, scratch_t(c, "mx_piece", (size_t)N, &piece));
-  GG_HIP(c, host_scratch_t(c, "mx_back", 2, &h_back));
-  size_t sort_bytes = 0, scan_bytes = 0, off_bytes = 0;
+  GG_HIP(c, host_scratch_t(c, "mx_back", 3, &h_back));
+  size_t sort_bytes = 0, scan_bytes = 0, off_bytes = 0, max_bytes = 0, red_bytes = 0;
   GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                                (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, 64));
   GG_HIP(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N));
   if (m > matrix::kMaxRows)
     GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, off_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                (int)(m + 1)));
-  const size_t tmp_bytes = std::max(std::max(sort_bytes, scan_bytes), off_bytes);
+  uint32_t *b_rows = nullptr, *b_new = nullptr;  // (the border) the row list; the new positions' kept entries
+  if (border) {
+    GG_HIP(c, hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                hipcub::Max(), (int)N));
+    GG_HIP(c, hipcub::DeviceReduce::Sum(nullptr, red_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_new));
+    GG_HIP(c, scratch_t(c, "mxb_rows", (size_t)m + 1, &b_rows));
+    b_new = b_rows + m;
+  }
+  const size_t tmp_bytes = std::max(std::max(std::max(sort_bytes, scan_bytes), off_bytes), std::max(max_bytes, red_bytes));
   uint8_t* tmp;
   GG_HIP(c, scratch_t(c, "mx_tmp", std::max<size_t>(tmp_bytes, 1), &tmp));
 
   size_t bytes = tmp_bytes;
+  if (border) {
+    hipLaunchKernelGGL(mxb_rows_kernel, grid_for(m), dim3(256), 0, st, n, border_n_old, b_rows);
+    GG_HIP(c, hipGetLastError());
+    d_rows = b_rows;
+  }
   if (m <= matrix::kMaxRows) {
     hipLaunchKernelGGL(mx_offsets_kernel, dim3(1), dim3(kOffBlock), 0, st, d_lens, n, s, d_rows, m, pos_row, pos_len,
                        pos_off);
@@ -505,22 +592,48 @@ gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const
                                                vals_out, (int)N, 0, 64, st));
   uint64_t* flags = keys_in;  // (the sort's input is free)
   uint32_t* id_of = vals_in;
-  hipLaunchKernelGGL(mx_flags_kernel, grid_for(N), dim3(256), 0, st, keys_out, N, pos_off, m, flags);
-  GG_HIP(c, hipGetLastError());
-  bytes = tmp_bytes;
-  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
-  hipLaunchKernelGGL(mx_ids_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, sums, pos_off, m, id_of);
-  GG_HIP(c, hipGetLastError());
+  if (border) {
+    // every entry's run start: the two u32 arrays that are free until the ids (vals_in) and the pieces are written
+    uint32_t *start_in = vals_in, *start1 = piece;
+    hipLaunchKernelGGL(mxb_starts_kernel, grid_for(N), dim3(256), 0, st, keys_out, N, pos_off, m, start_in);
+    GG_HIP(c, hipGetLastError());
+    bytes = tmp_bytes;
+    GG_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, bytes, (const uint32_t*)start_in, start1, hipcub::Max(), (int)N, st));
+    hipLaunchKernelGGL(mxb_flags_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, start1, N, pos_off, m, s,
+                       n_new, flags);
+    GG_HIP(c, hipGetLastError());
+    bytes = tmp_bytes;
+    GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
+    hipLaunchKernelGGL(mxb_ids_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, start1, sums, pos_off, m, s,
+                       n_new, id_of);
+    GG_HIP(c, hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(mx_flags_kernel, grid_for(N), dim3(256), 0, st, keys_out, N, pos_off, m, flags);
+    GG_HIP(c, hipGetLastError());
+    bytes = tmp_bytes;
+    GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
+    hipLaunchKernelGGL(mx_ids_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, sums, pos_off, m, id_of);
+    GG_HIP(c, hipGetLastError());
+  }
   hipLaunchKernelGGL(mx_pieces_kernel, dim3(m), dim3(256), 0, st, id_of, pos_len, s, piece, piece_cnt);
   GG_HIP(c, hipGetLastError());
   // entries, columns, column entries: the one read-back before the product
   GG_HIP(c, hipMemcpyAsync(&h_back[0], sums + (N - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   GG_HIP(c, hipMemcpyAsync(&h_back[1], pos_off + m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  h_back[2] = 0;
+  if (border && n_new) {  // with them, the kept entries of the new positions (the first n_new piece counts)
+    bytes = tmp_bytes;
+    GG_HIP(c, hipcub::DeviceReduce::Sum(tmp, bytes, (const uint32_t*)piece_cnt, b_new, (int)n_new, st));
+    GG_HIP(c, hipMemcpyAsync(&h_back[2], b_new, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  }
   GG_HIP(c, hipStreamSynchronize(st));
   const uint64_t n_columns = (uint32_t)h_back[0], column_entries = h_back[0] >> 32, n_entries = (uint32_t)h_back[1];
+  const uint64_t new_entries = (uint32_t)h_back[2];
   if (n_entries > N || column_entries > n_entries || 2 * n_columns > column_entries)
     return fail(c, GG_ERR_INTERNAL, std::string(who) + ": bad column counts");
-  *out = MatrixPrep{pos_row, pos_len, piece, piece_cnt, m, n_entries, n_columns, column_entries};
+  if (border && (new_entries > column_entries || new_entries < n_columns))
+    return fail(c, GG_ERR_INTERNAL, std::string(who) + ": bad border column counts");
+  *out = MatrixPrep{pos_row, pos_len, piece, piece_cnt, m, n_entries, n_columns, column_entries, new_entries};
   return GG_OK;
 }
 
@@ -599,6 +712,41 @@ gg_status pairs_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep&
   for (uint32_t base = 0; base < tile_pairs; base += std::min(slice, tile_pairs - base)) {
     a.wg_base = base;
     hipLaunchKernelGGL(mx_common_kernel<MxPairLaunch>, dim3(std::min(slice, tile_pairs - base)), dim3(256), 0, st, a);
+    GG_HIP(c, hipGetLastError());
+  }
+  return GG_OK;
+}
+
+// ---- the border form ----------------------------------------
+// The same over positions prepared with border_n_old = n - n_new: the border
+// tile pairs in slices, the cells of a new position only.  Asynchronous.
+gg_status pairs_border_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, uint32_t n_new,
+                                     const uint32_t* d_cmin, const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap,
+                                     uint64_t* d_count, hipStream_t st) {
+  if (p.m < 2 || n_new == 0) return GG_OK;
+  MxBorderLaunch a{};
+  a.sk = d_sk;
+  a.s = c->s;
+  a.m = p.m;
+  a.pos_row = p.pos_row;
+  a.pos_len = p.pos_len;
+  a.piece = p.piece;
+  a.piece_cnt = p.piece_cnt;
+  a.k = c->k;
+  a.count = (unsigned long long*)d_count;
+  a.cmin = d_cmin;
+  a.sufmin = d_sufmin;
+  a.tmax = 2 * c->s;
+  a.zero_passes = c->sufmin_host[0] == 0;
+  a.out = d_out;
+  a.out_cap = cap;
+  a.n_new = n_new;
+  a.tiles_new = matrix::tiles_of(n_new);
+  const uint32_t tile_pairs = matrix::border_tile_pairs(a.tiles_new, matrix::tiles_of(p.m));  // (< 2^31: border_limits_ok)
+  const uint32_t slice = test_pair_slice();
+  for (uint32_t base = 0; base < tile_pairs; base += std::min(slice, tile_pairs - base)) {
+    a.wg_base = base;
+    hipLaunchKernelGGL(mx_common_kernel<MxBorderLaunch>, dim3(std::min(slice, tile_pairs - base)), dim3(256), 0, st, a);
     GG_HIP(c, hipGetLastError());
   }
   return GG_OK;

@@ -3,8 +3,9 @@
 //   gg_pairs(rows[0:n]) == gg_pairs(rows[0:n_old]) U gg_pairs_border(rows[0:n], n_old)
 // with the sketch matrix left where it is (old rows first, new rows after
 // them).  K2 evaluates only the new rows (pairs_core with n_old: the border
-// forms of pairs_index.hip and pairs_gate.hip).  Every entry point here acts
-// on the context's first device.
+// forms of pairs_index.hip and pairs_gate.hip), or, by the context's pairs path
+// (gg_set_pairs_path), the border form of the matrix product
+// gives them.  Every entry point here acts on the context's first device.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -33,11 +34,17 @@ gg_status check_border_args(const char* who, const void* sketches, const uint32_
   return GG_OK;
 }
 
-// The border of n rows resident on m's device, in (i, j) order.
-gg_status border_to_host(gg_ctx* m, const uint64_t* d_sk, const uint32_t* d_len, uint32_t n, uint32_t n_old,
-                         float min_ani, std::vector<gg_pair>& res) {
+// The border of n rows resident on m's device, in (i, j) order: by the
+// context's pairs path the border form of the matrix product, else K2.
+gg_status border_to_host(gg_ctx* m, const char* who, const uint64_t* d_sk, const uint32_t* d_len, uint32_t n,
+                         uint32_t n_old, float min_ani, std::vector<gg_pair>& res) {
   if (n < 2 || n_old >= n) return GG_OK;
-  return pairs_range_to_host(m, d_sk, d_len, n, 0, gg_pair_tiles(n), min_ani, res, m->stream, n_old);
+  bool matrix = false;
+  gg_status st = border_routed_to_host(m, who, d_sk, d_len, n, n_old, min_ani, res, &matrix, m->stream);
+  if (st == GG_OK && !matrix)
+    st = pairs_range_to_host(m, d_sk, d_len, n, 0, gg_pair_tiles(n), min_ani, res, m->stream, n_old);
+  if (st == GG_OK) count_pairs_path(m, matrix);
+  return st;
 }
 
 gg_status pairs_border_ctx(gg_ctx* m, const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
@@ -52,7 +59,7 @@ gg_status pairs_border_ctx(gg_ctx* m, const uint64_t* sketches, const uint32_t* 
   GG_HIP(m, scratch_t(m, "bd_len", (size_t)n, &d_len));
   GG_HIP(m, hipMemcpyAsync(d_sk, sketches, (size_t)n * m->s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
   GG_HIP(m, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-  return border_to_host(m, d_sk, d_len, n, n_old, min_ani, res);
+  return border_to_host(m, "gg_pairs_border", d_sk, d_len, n, n_old, min_ani, res);
 }
 
 gg_status update_files_ctx(gg_ctx* m, const uint64_t* old_sketches, const uint32_t* old_lens, uint32_t n_old,
@@ -78,7 +85,7 @@ gg_status update_files_ctx(gg_ctx* m, const uint64_t* old_sketches, const uint32
   GG_HIP(m, hipMemcpyAsync(d_sk + (size_t)n_old * m->s, new_hashes, n_new * row, hipMemcpyHostToDevice, m->stream));
   GG_HIP(m, hipMemcpyAsync(d_len + n_old, new_lens, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice,
                            m->stream));
-  return border_to_host(m, d_sk, d_len, n, n_old, min_ani, res);
+  return border_to_host(m, "gg_update_files", d_sk, d_len, n, n_old, min_ani, res);
 }
 
 }  // namespace
@@ -155,8 +162,13 @@ gg_status gg_pairs_border_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
   if (n < 2 || n_old == n) return GG_OK;
   gg_ctx* m = primary(ctx);
   if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  const gg_status st = pairs_core(m, d_sketches, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, out_cap, d_count,
-                                  (hipStream_t)stream, n_old);
+  bool matrix = false;
+  gg_status st = border_routed_append(m, "gg_pairs_border_device", d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap,
+                                      d_count, &matrix, (hipStream_t)stream);
+  if (st == GG_OK && !matrix)
+    st = pairs_core(m, d_sketches, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, out_cap, d_count, (hipStream_t)stream,
+                    n_old);
+  if (st == GG_OK) count_pairs_path(m, matrix);
   if (st != GG_OK && m != ctx) ctx->err = m->err;
   return st;
 }

@@ -292,19 +292,30 @@ gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32
                                    hipStream_t st);
 // The positions part of a matrix call (ani_matrix.hip), in context scratch
 // until the next matrix call on the context, and the counts read back.
+// border_n_old != kNoBorder (then m == n >= border_n_old, d_rows is not read):
+// the border form (matrix_core.hpp) -- the new rows at the first positions,
+// the border column rule, and new_entries, the kept entries of the new rows.
+constexpr uint32_t kNoBorder = 0xFFFFFFFFu;
 struct MatrixPrep {
   const uint32_t *pos_row, *pos_len, *piece, *piece_cnt;
   uint32_t m;
   uint64_t n_entries, n_columns, column_entries;
+  uint64_t new_entries = 0;
 };
 gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st);
+                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st,
+                         uint32_t border_n_old = kNoBorder);
 // The pair form of the product (ani_matrix.hip, matrix_core.hpp): the passing
 // pairs of the prepared positions appended to d_out, gg_pairs_device's output
 // contract.  d_cmin / d_sufmin: pairs_tables'.  Asynchronous.
 gg_status pairs_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, const uint32_t* d_cmin,
                               const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
                               hipStream_t st);
+// The border form of it over positions prepared with
+// border_n_old = p.m - n_new.  Asynchronous.
+gg_status pairs_border_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, uint32_t n_new,
+                                     const uint32_t* d_cmin, const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap,
+                                     uint64_t* d_count, hipStream_t st);
 // cmin / sufmin of min_ani on the device, as every pair kernel takes them
 // (api.cpp's ensure_cmin; c->sufmin_host[0] == 0: some pair without a shared hash passes)
 gg_status pairs_tables(gg_ctx* c, float min_ani, uint32_t** d_cmin, uint32_t** d_sufmin, hipStream_t st);
@@ -321,6 +332,21 @@ gg_status sorted_pairs_device(gg_ctx* c, const gg_pair* d_pairs, uint64_t cnt, u
 gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                             float min_ani, gg_pair** d_out, uint64_t* cnt, uint32_t* passes, hipStream_t st,
                             gg_pairs_matrix_summary* msum = nullptr);
+// A border call (border.cpp) of n >= 2 resident rows, n_old < n, by the
+// context's pairs path (resident.cpp).  *ran false: nothing
+// was emitted and the caller runs the index border as ever (DEFAULT, which
+// runs nothing here, or AUTO's choice after the border positions part); true:
+// the border form of the matrix product gave the pairs -- appended to res in
+// (i, j) order (sized passes into context scratch, sorted on the device;
+// synchronises st), or appended to d_out by gg_pairs_border_device's contract
+// (synchronises st once, before the product).  count_pairs_path counts the
+// call for gg_pairs_paths_taken once it has succeeded.
+gg_status border_routed_to_host(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                                uint32_t n_old, float min_ani, std::vector<gg_pair>& res, bool* ran, hipStream_t st);
+gg_status border_routed_append(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                               uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count, bool* ran,
+                               hipStream_t st);
+void count_pairs_path(gg_ctx* c, bool matrix);
 // Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
 // ani_f32_device, cluster_device; with sum, the partition of
 // preclusters_device.  *d_pairs / *d_ani (may be null) receive the scratch

@@ -199,15 +199,95 @@ inline uint64_t pair_index_reads(uint64_t n_columns, uint64_t column_entries) {
   return n_columns ? column_entries * column_entries / n_columns : 0;  // (column_entries < 2^31)
 }
 
+// ---- the border form -----------------------------------------------
+// The pair form over rows 0 .. n-1 of which the last n_new = n - n_old are new:
+// only the pairs that involve a new row (gg_pairs_border's set), so that the
+// product can leave out most of its tile pairs and most of its columns.
+//   Positions.  Position a names row n_old + a for a < n_new and row a - n_new
+//     otherwise: the new rows come first, the sketch matrix is not moved (the
+//     positions part is given this map as its row list).
+//   Cells visited.  pair_visited and pa < n_new: every new x new pair once,
+//     every new x old pair once; in the tile row that holds new and old
+//     positions (n_new % kTile != 0) the cells with pa >= n_new are skipped.
+//     The emitted record is the pair form's, (old, new) for a new x old cell.
+//   Tile pairs.  ti < Tn = tiles_of(n_new) and ti <= tj < T = tiles_of(n):
+//     the first Tn (Tn + 1) / 2 workgroups are the pair form's triangle over
+//     the new tiles (tile_pair_of); workgroup p' behind them is tj = Tn +
+//     p' / Tn, ti = p' % Tn, a rectangle of Tn x (T - Tn).  Slices of
+//     kPairSlice and wg_base as in the pair form.
+//   The border column rule.  A column is a distinct hash held at two or more
+//     positions, at least one of them new: a hash shared among old rows only
+//     adds nothing to a visited cell and is dropped (an old row unrelated to
+//     every new row has an empty piece, its tile pairs take the early exit).
+//     After the stable sort of (hash, slot), slots in position order, the
+//     first entry of a run of equal hashes is the run's lowest position: a run
+//     is kept iff it has two entries or more and that position is < n_new.
+//   Unchanged.  The candidate test, the pass test, the empty-row rule,
+//     zero_passes and the early exit; total comes from the rank search on the
+//     full rows, so a dropped column changes no total.
+//   Limits.  n_old <= n, n s < 2^31 sketch slots, fewer than 2^31 border tile
+//     pairs.  n_old == n: nothing; n_old == 0: the pair form over all rows.
+GG_MATRIX_HD inline uint32_t border_row_of(uint32_t a, uint32_t n, uint32_t n_old) {
+  const uint32_t n_new = n - n_old;
+  return a < n_new ? n_old + a : a - n_new;
+}
+GG_MATRIX_HD inline bool border_visited(uint32_t pa, uint32_t pb, uint32_t n_new, uint32_t row_a, uint32_t row_b) {
+  return pa < n_new && pair_visited(pa, pb, row_a, row_b);
+}
+// a run of equal hashes whose first entry lies at position head_pos is a border column (given two entries or more)
+GG_MATRIX_HD inline bool border_column_kept(uint32_t head_pos, uint32_t n_new) { return head_pos < n_new; }
+// (tiles_new <= tiles; the result < 2^31: border_limits_ok)
+GG_MATRIX_HD inline uint32_t border_tile_pairs(uint32_t tiles_new, uint32_t tiles) {
+  return tile_pairs_of(tiles_new) + tiles_new * (tiles - tiles_new);
+}
+// workgroup p -> (ti < tiles_new, ti <= tj)
+GG_MATRIX_HD inline void border_tile_pair_of(uint32_t p, uint32_t tiles_new, uint32_t* ti, uint32_t* tj) {
+  const uint32_t tri = tile_pairs_of(tiles_new);
+  if (p < tri) {
+    tile_pair_of(p, ti, tj);
+  } else {
+    const uint32_t q = p - tri;
+    *tj = tiles_new + q / tiles_new;
+    *ti = q % tiles_new;
+  }
+}
+// its inverse
+GG_MATRIX_HD inline uint32_t border_tile_pair_index(uint32_t ti, uint32_t tj, uint32_t tiles_new) {
+  return tj < tiles_new ? tj * (tj + 1) / 2 + ti : tile_pairs_of(tiles_new) + (tj - tiles_new) * tiles_new + ti;
+}
+inline bool border_limits_ok(uint64_t n, uint64_t n_old, uint64_t sketch_size) {
+  if (n_old > n || n * sketch_size >= (1ull << 31) || n >= (1ull << 31)) return false;
+  const uint64_t tiles = (n + kTile - 1) / kTile, tiles_new = (n - n_old + kTile - 1) / kTile;  // (< 2^25)
+  return tiles_new * (tiles_new + 1) / 2 + tiles_new * (tiles - tiles_new) < (1ull << 31);
+}
+// AUTO's two bounds for a border, from the counts the positions part reads
+// back: the kept columns, their entries, and those of them at new positions.
+// The index border kernel lets every new entry read the members before it: a
+// column held by a new and b old rows (a >= 1, a + b >= 2; the new rows are
+// its last members) costs a b + a (a - 1) / 2 reads.  Over the columns,
+// sum a b >= sum b = old_entries (a >= 1), and sum a (a - 1) / 2 >=
+// (new_entries^2 / n_columns - new_entries) / 2 (Cauchy-Schwarz; the left side
+// is an integer, so the floors only lower the right; new_entries >= n_columns).
+inline uint64_t border_chunk_rounds(uint64_t n, uint64_t n_old, uint64_t n_columns) {
+  const uint64_t tiles = (n + kTile - 1) / kTile, tiles_new = (n - n_old + kTile - 1) / kTile;
+  return (tiles_new * (tiles_new + 1) / 2 + tiles_new * (tiles - tiles_new)) * ((n_columns + kChunk - 1) / kChunk);
+}
+inline uint64_t border_index_reads(uint64_t n_columns, uint64_t column_entries, uint64_t new_entries) {
+  if (!n_columns) return 0;  // (new_entries <= column_entries < 2^31)
+  return (column_entries - new_entries) + (new_entries * new_entries / n_columns - new_entries) / 2;
+}
+
 // ---- the columns on the host ------------------------------------------------------
 // What the device builds with a radix sort and a scan: piece[a] the ascending
-// column ids of position a.  rows == nullptr: position a is row a.
+// column ids of position a.  rows == nullptr: position a is row a.  n_new <
+// kNoColumn: the border column rule with the first n_new positions new
+// (new_entries then counts their kept entries).
 struct Columns {
-  uint64_t n_entries = 0, n_columns = 0, column_entries = 0;
+  uint64_t n_entries = 0, n_columns = 0, column_entries = 0, new_entries = 0;
   std::vector<std::vector<uint32_t>> piece;
 };
 inline Columns columns_host(const uint64_t* sketches, const uint32_t* lens, uint32_t sketch_size, const uint32_t* rows,
-                            uint32_t m) {
+                            uint32_t m, uint32_t n_new = kNoColumn) {
   struct Key {
     uint64_t hash;
     uint64_t slot;
@@ -224,8 +304,11 @@ inline Columns columns_host(const uint64_t* sketches, const uint32_t* lens, uint
   Columns c;
   c.n_entries = K.size();
   std::vector<uint32_t> id_of((size_t)m * sketch_size, kNoColumn);
-  uint64_t sum = 0;
+  uint64_t sum = 0, head = 0;  // head: the first entry of the run of equal hashes that holds i
   for (uint64_t i = 0; i < K.size(); ++i) {
+    if (i == 0 || K[i] != K[i - 1]) head = i;
+    const bool kept = n_new == kNoColumn || border_column_kept((uint32_t)(keys[head].slot / sketch_size), n_new);
+    if (!kept) continue;
     sum += column_flags(K.data(), i, K.size());
     if (in_column(K.data(), i, K.size())) id_of[keys[i].slot] = column_id(sum);
   }
@@ -236,6 +319,7 @@ inline Columns columns_host(const uint64_t* sketches, const uint32_t* lens, uint
     const uint32_t g = rows ? rows[a] : a;
     for (uint32_t e = 0; e < lens[g]; ++e)
       if (id_of[(size_t)a * sketch_size + e] != kNoColumn) c.piece[a].push_back(id_of[(size_t)a * sketch_size + e]);
+    if (n_new != kNoColumn && a < n_new) c.new_entries += c.piece[a].size();
   }
   return c;
 }

@@ -29,12 +29,13 @@ namespace {
 // GALAHGPU_PAIRS_MATRIX_RATIO, read per call: AUTO takes the product when the
 // index's member reads exceed R chunk rounds (changes no result)
 constexpr double kPairsMatrixRatio = 3675.0;  // (measured)
-double pairs_matrix_ratio() {
+constexpr double kBorderMatrixRatio = 1000.0;  // a border call's (measured)
+double pairs_matrix_ratio(double dflt = kPairsMatrixRatio) {
   const char* e = getenv("GALAHGPU_PAIRS_MATRIX_RATIO");
-  if (!e || !*e) return kPairsMatrixRatio;
+  if (!e || !*e) return dflt;
   char* end = nullptr;
   const double v = strtod(e, &end);
-  return end == e || std::isnan(v) ? kPairsMatrixRatio : v;
+  return end == e || std::isnan(v) ? dflt : v;
 }
 
 // GALAHGPU_TEST_PAIRS_CAP, read per call: lowers gg_pairs_matrix's first capacity (tests of the retry)
@@ -244,6 +245,180 @@ gg_status pairs_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* 
   return GG_OK;
 }
 
+// ---- the border form ------------------------------------------
+namespace {
+
+uint64_t border_all_pairs(uint32_t n, uint32_t n_old) {
+  const uint64_t n_new = n - n_old;
+  return n_new * n_old + n_new * (n_new - 1) / 2;
+}
+
+void fill_border_summary(gg_pairs_matrix_summary* sum, const MatrixPrep& p, uint32_t n_old) {
+  sum->n_entries = p.n_entries;
+  sum->n_columns = p.n_columns;
+  sum->column_entries = p.column_entries;
+  sum->chunk_rounds = matrix::border_chunk_rounds(p.m, n_old, p.n_columns);
+  sum->index_reads = matrix::border_index_reads(p.n_columns, p.column_entries, p.new_entries);
+}
+
+// gg_pairs_border_matrix_device behind its argument checks (n >= 2, n_old < n)
+gg_status pairs_border_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, uint32_t n_old,
+                                     float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
+                                     gg_pairs_matrix_summary* sum, hipStream_t st) {
+  const char* who = "gg_pairs_border_matrix";
+  uint64_t* h_count = nullptr;
+  if (sum) {  // the count before, read with the positions part's read-back
+    GG_HIP(c, host_scratch_t(c, "pm_count", 2, &h_count));
+    GG_HIP(c, hipMemcpyAsync(&h_count[0], d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  }
+  MatrixPrep prep;
+  gg_status r = matrix_prepare(c, who, d_sk, d_lens, n, nullptr, n, &prep, st, n_old);
+  if (r != GG_OK) return r;
+  uint32_t *d_cmin, *d_sufmin;
+  r = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
+  if (r != GG_OK) return r;
+  r = pairs_border_matrix_launch(c, d_sk, prep, n - n_old, d_cmin, d_sufmin, d_out, cap, d_count, st);
+  if (r != GG_OK) return r;
+  if (sum) {
+    GG_HIP(c, hipMemcpyAsync(&h_count[1], d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    GG_HIP(c, hipStreamSynchronize(st));
+    fill_border_summary(sum, prep, n_old);
+    sum->n_pairs = h_count[1] - h_count[0];
+    sum->path = GG_PAIRS_PATH_MATRIX;
+    sum->pair_passes = 1;
+  }
+  return GG_OK;
+}
+
+// The border of prepared positions into context scratch, sorted by (i, j):
+// the first capacity min(all border pairs, max(2^20, 16 n)), one retry at the
+// exact count.
+gg_status border_matrix_sorted(gg_ctx* c, const char* who, const uint64_t* d_sk, const MatrixPrep& prep, uint32_t n,
+                               uint32_t n_old, float min_ani, gg_pair** d_sorted, uint64_t* cnt, uint32_t* passes,
+                               hipStream_t st) {
+  const uint64_t all = border_all_pairs(n, n_old);
+  const uint64_t cap = test_pairs_cap(std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all));
+  gg_pair* d_pairs = nullptr;
+  uint32_t *d_cmin, *d_sufmin;
+  const gg_status r = sized_pair_passes(
+      c, who, "pm_pairs", all, cap,
+      [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) {
+        const gg_status t = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
+        return t != GG_OK ? t
+                          : pairs_border_matrix_launch(c, d_sk, prep, n - n_old, d_cmin, d_sufmin, d_out, pcap, d_count, st);
+      },
+      &d_pairs, cnt, passes, st);
+  if (r != GG_OK) return r;
+  return sorted_pairs_device(c, d_pairs, *cnt, n, d_sorted, st);
+}
+
+// gg_pairs_border_matrix behind its context lookup: host arrays in, the sorted list out
+gg_status pairs_border_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
+                                  float min_ani, gg_pair** out, uint64_t* n_out, gg_pairs_matrix_summary* sum) {
+  const char* who = "gg_pairs_border_matrix";
+  if (!out || !n_out) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  *out = nullptr;
+  *n_out = 0;
+  if (std::isnan(min_ani)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": min_ani is NaN");
+  if (n_old > n) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": n_old exceeds n");
+  if (!matrix::border_limits_ok(n, n_old, c->s))
+    return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more");
+  if (n && (!sketches || !lens)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
+  for (uint32_t g = 0; g < n; ++g)
+    if (lens[g] > c->s) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": sketch longer than sketch_size");
+  if (n < 2 || n_old == n) {  // no pair: nothing is run
+    if (sum) sum->path = GG_PAIRS_PATH_MATRIX;
+    *out = (gg_pair*)malloc(sizeof(gg_pair));
+    return *out ? GG_OK : fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+  }
+  if (hipSetDevice(c->device) != hipSuccess) return fail(c, GG_ERR_HIP, "hipSetDevice failed");
+  hipStream_t st = c->stream;
+  uint64_t* d_sk = nullptr;
+  uint32_t* d_len = nullptr;
+  GG_HIP(c, scratch_t(c, "mx_h_sk", (size_t)n * c->s, &d_sk));
+  GG_HIP(c, scratch_t(c, "mx_h_len", (size_t)n, &d_len));
+  GG_HIP(c, hipMemcpyAsync(d_sk, sketches, (size_t)n * c->s * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  GG_HIP(c, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  MatrixPrep prep;
+  gg_status r = matrix_prepare(c, who, d_sk, d_len, n, nullptr, n, &prep, st, n_old);
+  if (r != GG_OK) return r;
+  gg_pair* d_sorted = nullptr;
+  uint64_t cnt = 0;
+  uint32_t passes = 0;
+  r = border_matrix_sorted(c, who, d_sk, prep, n, n_old, min_ani, &d_sorted, &cnt, &passes, st);
+  if (r != GG_OK) return r;
+  *out = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
+  if (!*out) return fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+  if (cnt) GG_HIP(c, hipMemcpyAsync(*out, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
+  GG_HIP(c, hipStreamSynchronize(st));
+  *n_out = cnt;
+  if (sum) {
+    fill_border_summary(sum, prep, n_old);
+    sum->n_pairs = cnt;
+    sum->path = GG_PAIRS_PATH_MATRIX;
+    sum->pair_passes = passes;
+  }
+  return GG_OK;
+}
+
+// The route of a border call of n >= 2 rows, n_old < n, by the context's pairs
+// path.  DEFAULT: nothing is run.  MATRIX: the border positions part, or
+// GG_ERR_INVALID_ARG when the limits fail.  AUTO: the positions part when the
+// limits hold, and the product iff there is a column and index_reads > R *
+// chunk_rounds (R: GALAHGPU_PAIRS_MATRIX_RATIO, by default a border's own
+// 1,000).
+gg_status border_route(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                       uint32_t n_old, hipStream_t st, bool* matrix, MatrixPrep* prep) {
+  *matrix = false;
+  if (c->pairs_path == GG_PAIRS_PATH_DEFAULT) return GG_OK;
+  const bool fits = matrix::border_limits_ok(n, n_old, c->s);
+  if (c->pairs_path == GG_PAIRS_PATH_MATRIX && !fits)
+    return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more, on the matrix path");
+  if (!fits) return GG_OK;
+  const gg_status r = matrix_prepare(c, who, d_sk, d_lens, n, nullptr, n, prep, st, n_old);
+  if (r != GG_OK) return r;
+  gg_pairs_matrix_summary ms{};
+  fill_border_summary(&ms, *prep, n_old);
+  *matrix = c->pairs_path == GG_PAIRS_PATH_MATRIX ||
+            (prep->n_columns > 0 && (double)ms.index_reads > pairs_matrix_ratio(kBorderMatrixRatio) * (double)ms.chunk_rounds);
+  return GG_OK;
+}
+
+}  // namespace
+
+void count_pairs_path(gg_ctx* c, bool matrix) {
+  ++c->pairs_paths_taken[!matrix ? 0 : c->pairs_path == GG_PAIRS_PATH_MATRIX ? 1 : 2];
+}
+
+gg_status border_routed_to_host(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                                uint32_t n_old, float min_ani, std::vector<gg_pair>& res, bool* ran, hipStream_t st) {
+  MatrixPrep prep{};
+  gg_status r = border_route(c, who, d_sk, d_lens, n, n_old, st, ran, &prep);
+  if (r != GG_OK || !*ran) return r;
+  gg_pair* d_sorted = nullptr;
+  uint64_t cnt = 0;
+  uint32_t passes = 0;
+  r = border_matrix_sorted(c, who, d_sk, prep, n, n_old, min_ani, &d_sorted, &cnt, &passes, st);
+  if (r != GG_OK) return r;
+  const size_t at = res.size();
+  res.resize(at + cnt);
+  if (cnt) GG_HIP(c, hipMemcpyAsync(res.data() + at, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
+  GG_HIP(c, hipStreamSynchronize(st));
+  return GG_OK;
+}
+
+gg_status border_routed_append(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                               uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count, bool* ran,
+                               hipStream_t st) {
+  MatrixPrep prep{};
+  gg_status r = border_route(c, who, d_sk, d_lens, n, n_old, st, ran, &prep);
+  if (r != GG_OK || !*ran) return r;
+  uint32_t *d_cmin, *d_sufmin;
+  r = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
+  if (r != GG_OK) return r;
+  return pairs_border_matrix_launch(c, d_sk, prep, n - n_old, d_cmin, d_sufmin, d_out, cap, d_count, st);
+}
+
 gg_status cluster_rows_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, float min_ani,
                               float T, uint32_t* d_rep_of, gg_cluster_summary* sum, const gg_pair** d_pairs,
                               const float** d_ani, hipStream_t st) {
@@ -346,6 +521,54 @@ gg_status gg_pairs_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t*
   gg_ctx* pm = primary(ctx);
   if (summary) *summary = gg_pairs_matrix_summary{};
   const gg_status st = pairs_matrix_ctx(pm, sketches, lens, n, rows, m, min_ani, out, n_out, summary);
+  if (st != GG_OK) {
+    if (out) {
+      free(*out);
+      *out = nullptr;
+    }
+    if (n_out) *n_out = 0;
+    if (summary) *summary = gg_pairs_matrix_summary{};
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
+}
+
+gg_status gg_pairs_border_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                        uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t out_cap,
+                                        uint64_t* d_count, gg_pairs_matrix_summary* summary, void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  gg_ctx* pm = primary(ctx);
+  gg_status st = GG_OK;
+  if (summary) *summary = gg_pairs_matrix_summary{};
+  const bool work = n >= 2 && n_old < n;
+  if (std::isnan(min_ani))
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: min_ani is NaN");
+  else if (n_old > n)  // (the limits: before any buffer is looked at)
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: n_old exceeds n");
+  else if (!matrix::border_limits_ok(n, n_old, pm->s))
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: 2^31 sketch slots or tile pairs, or more");
+  else if (work && (!d_sketches || !d_lens || !d_count || (out_cap && !d_out)))
+    st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: null buffer");
+  else if (!work) {  // no pair: nothing is run, the count is left as it is
+    if (summary) summary->path = GG_PAIRS_PATH_MATRIX;
+  } else if (hipSetDevice(pm->device) != hipSuccess)
+    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  else
+    st = pairs_border_matrix_device(pm, d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count, summary,
+                                    (hipStream_t)stream);
+  if (st != GG_OK) {
+    if (summary) *summary = gg_pairs_matrix_summary{};
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
+}
+
+gg_status gg_pairs_border_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
+                                 float min_ani, gg_pair** out, uint64_t* n_out, gg_pairs_matrix_summary* summary) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+  gg_ctx* pm = primary(ctx);
+  if (summary) *summary = gg_pairs_matrix_summary{};
+  const gg_status st = pairs_border_matrix_ctx(pm, sketches, lens, n, n_old, min_ani, out, n_out, summary);
   if (st != GG_OK) {
     if (out) {
       free(*out);

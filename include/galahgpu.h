@@ -212,7 +212,9 @@ gg_status gg_pairs_device(gg_ctx* ctx, const uint64_t* d_sketches,
  * the new rows, each against every row before it.  n_old == 0 gives
  * gg_pairs, n_old == n nothing, n_old > n GG_ERR_INVALID_ARG.  A multi-device
  * context acts on its first member (the border is not sharded).
- * gg_pair_paths and gg_fallbacks count a border call like any other. */
+ * gg_pair_paths and gg_fallbacks count a border call like any other.  Under
+ * gg_set_pairs_path MATRIX or AUTO these calls take the border form of the
+ * matrix product instead (gg_pairs_border_matrix, below): the same pairs. */
 
 /* Host buffers in and out, as gg_pairs: *out library-owned (gg_free), sorted
  * by (i, j); lens[g] <= sketch_size is checked. */
@@ -715,14 +717,49 @@ gg_status gg_pairs_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
 gg_status gg_pairs_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
                           const uint32_t* rows, uint32_t m, float min_ani, gg_pair** out, uint64_t* n_out,
                           gg_pairs_matrix_summary* summary);
+/* The border (gg_pairs_border's set: the pairs (i < j) of rows 0 .. n-1 with
+ * j >= n_old) from the same product: the new rows take the
+ * first positions (the sketch matrix is not moved), only tile pairs with a new
+ * tile and cells of a new row are evaluated, and a hash shared among old rows
+ * only is no column, so that old rows unrelated to every new row cost a
+ * search and no product.  Limits, GG_ERR_INVALID_ARG before any row is read:
+ * n_old <= n, n * sketch size < 2^31, fewer than 2^31 border tile pairs
+ * (ceil(n_new / 64) tiles of new rows against all that follow them).
+ * n_old == n gives nothing and launches nothing (*d_count is left as it is);
+ * n_old == 0 is gg_pairs_matrix over all rows.  In the summary n_columns and
+ * column_entries count the border's columns, chunk_rounds is the border tile
+ * pairs x ceil(n_columns / 512), and index_reads is a lower bound of the
+ * member reads of the index border kernel, in which every new entry reads the
+ * members before it: (column_entries - e) + (e^2 / n_columns - e) / 2 with e
+ * the column entries of the new rows (0 without columns).
+ *
+ * Device-resident: gg_pairs_border_device's output contract (appends unsorted
+ * to d_out, *d_count grown by the number found, nothing written past out_cap);
+ * synchronises the stream as gg_pairs_matrix_device does.  summary may be NULL. */
+gg_status gg_pairs_border_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                                        uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t out_cap,
+                                        uint64_t* d_count, gg_pairs_matrix_summary* summary, void* stream);
+/* Host arrays in; *out library-owned (gg_free), sorted by (i, j) on the
+ * device, as gg_pairs_border gives it.  lens[g] <= sketch_size is checked.
+ * The first output capacity is min(all border pairs, max(2^20, 16 n)), with
+ * one retry at the exact count.  A multi-device context acts on its first
+ * member. */
+gg_status gg_pairs_border_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                                 uint32_t n_old, float min_ani, gg_pair** out, uint64_t* n_out,
+                                 gg_pairs_matrix_summary* summary);
 /* What produces the pairs inside gg_cluster_rows_device,
- * gg_cluster_files_resident, gg_precluster_matrices_files and
- * gg_precluster_files_resident.  DEFAULT (a new context's): K2 as ever.
- * MATRIX: the pair form over all rows (GG_ERR_INVALID_ARG from those calls
- * when the limits do not hold).  AUTO: the positions part of the matrix call
- * is run and its three counts read back; the product is taken iff there is a
+ * gg_cluster_files_resident, gg_precluster_matrices_files,
+ * gg_precluster_files_resident and the border calls gg_pairs_border,
+ * gg_pairs_border_device and gg_update_files.  DEFAULT (a new context's): K2
+ * as ever.  MATRIX: the pair form over all rows, for a border call the border
+ * form (GG_ERR_INVALID_ARG from those calls when the limits do not hold).
+ * AUTO: the positions part of the matrix call (a border call: of the border
+ * form) is run and its counts read back; the product is taken iff there is a
  * column, the limits hold and index_reads > R * chunk_rounds (R:
- * GALAHGPU_PAIRS_MATRIX_RATIO), else K2 exactly as DEFAULT.
+ * GALAHGPU_PAIRS_MATRIX_RATIO, by default 3,675, and 1,000 for a border call:
+ * DESIGN.md 4.12, 4.13), else K2 exactly as DEFAULT.
+ * Under MATRIX and AUTO gg_pairs_border_device synchronises its stream once
+ * (the positions part's read-back); under DEFAULT it stays asynchronous.
  * AUTO pays the 64-bit sort of n * sketch size slots (about 0.9 ms per 10^7)
  * even when it then runs K2, which is why it is not the default.  The results
  * do not depend on the path.  An unknown value is GG_ERR_INVALID_ARG.  A

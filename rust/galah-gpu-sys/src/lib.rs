@@ -389,6 +389,13 @@ extern "C" {
     pub fn gg_pairs_matrix(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, rows: *const u32,
                            m: u32, min_ani: f32, out: *mut *mut gg_pair, n_out: *mut u64,
                            summary: *mut gg_pairs_matrix_summary) -> GgStatus;
+    pub fn gg_pairs_border_matrix_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32,
+                                         n_old: u32, min_ani: f32, d_out: *mut gg_pair, out_cap: u64,
+                                         d_count: *mut u64, summary: *mut gg_pairs_matrix_summary,
+                                         stream: *mut c_void) -> GgStatus;
+    pub fn gg_pairs_border_matrix(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, n_old: u32,
+                                  min_ani: f32, out: *mut *mut gg_pair, n_out: *mut u64,
+                                  summary: *mut gg_pairs_matrix_summary) -> GgStatus;
     pub fn gg_set_pairs_path(ctx: *mut gg_ctx, path: c_int) -> GgStatus;
     pub fn gg_pairs_path(ctx: *const gg_ctx) -> c_int;
     pub fn gg_pairs_paths_taken(ctx: *const gg_ctx, counts: *mut u64) -> GgStatus;
