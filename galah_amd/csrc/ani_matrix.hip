@@ -4,19 +4,40 @@
 // incidence matrix A [positions x columns], common = A A^T, on the i8 matrix
 // instruction.
 //
+// The positions part -- matrix_prepare, the one of all four forms (DESIGN.md
+// 4.14); a MatrixForm selects the three places in which the forms differ:
+//
 //   mx_offsets_kernel  one workgroup: every position's row, length and the
-//                      exclusive sum of the lengths.
+//                      exclusive sum of the lengths (the dense form, and the
+//                      pair and border forms up to kMaxRows rows); else
+//   mx_positions_kernel<groups> and hipcub ExclusiveSum: the same for any
+//                      number of positions, with every position's group.
+//                      [border: mxb_rows_kernel before it, the new rows first;
+//                       groups: mxg_segments_kernel, every group's first entry]
 //   mx_keys_kernel     (hash, slot = position * s + e) of every entry, the
 //                      valid ones packed to the front, the others (key ~0)
 //                      behind them, so the sort's count needs no read-back.
 //   hipcub SortPairs   on the 64-bit key (stable: the padding stays behind).
-//   mx_flags_kernel    the column rule on the sorted keys, both flags packed;
+//                      [two groups or more: mxg_entry_groups_kernel, a stable
+//                       SortPairs on the group's bits, mxg_gather_kernel -- the
+//                       entries by (group, hash); one group: a memset]
+//                      [border: mxb_starts_kernel and an inclusive max, every
+//                       entry's first entry of its run of equal hashes]
+//   mx_flags_kernel<Rule>  the column rule on the sorted keys, both flags
+//                      packed: PlainRule, BorderRule (the runs whose first entry
+//                      lies at a new position) or GroupRule (within a group);
 //   hipcub InclusiveSum  column ids and, at the end, the two counts.
-//   mx_ids_kernel      the id (or none) of every entry, scattered to its slot.
+//   mx_ids_kernel<Rule>  the id (or none) of every entry, scattered to its
+//                      slot (GroupRule: local to the group).
 //   mx_pieces_kernel   one workgroup per position: its kept ids compacted in
 //                      order into a contiguous piece with a count.
-//   [read back: entries, columns, column entries -- the one sync before the product]
+//   [read back: entries, columns, column entries, and a border's new entries
+//    -- the one sync before the product]
 //   mx_common_kernel   the product and the epilogue, below.
+//
+// Flags and ids live in whichever of the two sort buffers the sorted keys and
+// slots are not in; a border's run starts in the value buffer the ids go to
+// later and in the piece buffer.
 //
 // mx_common_kernel: one workgroup (4 waves) per tile pair ti <= tj of 64 x 64
 // positions, K over the columns in chunks of 512.  Per chunk: one thread per
@@ -49,18 +70,17 @@
 // the rank search only when its common can pass, and the passing pairs are
 // staged in the image area (free after the loop's last barrier), counted with
 // one LDS add per wave and step, and appended to the output with one global
-// add per workgroup and 16-byte stores.  matrix_prepare is the positions part
-// shared by the dense and the pair form; beyond kMaxRows rows (the pair form
-// only) the offsets come from mxp_positions_kernel and a scan.
+// add per workgroup and 16-byte stores.
 //
 // The border form is the fourth instantiation, on
 // MxBorderLaunch: the pair form over rows of which the last n_new are new,
 // with the new rows at the first positions (mxb_rows_kernel writes the map as
 // a row list), the tile pairs that hold a new tile only, the cells of a new
-// position only, and the border column rule in the positions part:
-// mxb_starts_kernel and an inclusive max give every sorted entry the first
-// entry of its run of equal hashes, mxb_flags_kernel / mxb_ids_kernel keep the
-// runs whose first entry lies at a new position.
+// position only, and the border column rule in the positions part.
+//
+// Around the kernel the forms share launch_of (the fields of every launch),
+// dense_product (the dense and the grouped tail) and launch_pair_slices (the
+// pair and the border launches).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -133,14 +153,18 @@ __global__ __launch_bounds__(kOffBlock) void mx_offsets_kernel(const uint32_t* _
   if (t == kOffBlock - 1) pos_off[m] = part[t];
 }
 
-// the same rows and lengths for any number of positions (the pair form beyond
-// kMaxRows): len1[0 .. m] the lengths and a 0 behind them, for the scan that
-// gives pos_off
-__global__ __launch_bounds__(256) void mxp_positions_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
-                                                            const uint32_t* __restrict__ rows, uint32_t m,
-                                                            uint32_t* __restrict__ pos_row,
-                                                            uint32_t* __restrict__ pos_len,
-                                                            uint32_t* __restrict__ len1) {
+// the same rows and lengths for any number of positions (the pair and border
+// forms beyond kMaxRows, the grouped form always): len1[0 .. m] the lengths and
+// a 0 behind them (the scan's last item: its exclusive sum is the number of
+// entries), for the scan that gives pos_off.  kGroups: len1 is pos_len itself,
+// of m + 1 words, and pos_grp[a] the position's group (a search of offsets)
+template <bool kGroups>
+__global__ __launch_bounds__(256) void mx_positions_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
+                                                           const uint32_t* __restrict__ rows, uint32_t m,
+                                                           uint32_t* __restrict__ pos_row, uint32_t* __restrict__ pos_len,
+                                                           uint32_t* __restrict__ len1,
+                                                           const uint32_t* __restrict__ offsets, uint32_t n_groups,
+                                                           uint32_t* __restrict__ pos_grp) {
   for (uint32_t a = blockIdx.x * 256 + threadIdx.x; a <= m; a += gridDim.x * 256) {
     if (a == m) {
       len1[a] = 0;
@@ -151,7 +175,8 @@ __global__ __launch_bounds__(256) void mxp_positions_kernel(const uint32_t* __re
     const uint32_t len = ok ? min(lens[g], s) : 0u;
     pos_row[a] = ok ? g : kNoRow;
     pos_len[a] = len;
-    len1[a] = len;
+    if constexpr (kGroups) pos_grp[a] = matrix::group_of_position(offsets, n_groups, a);
+    else len1[a] = len;
   }
 }
 
@@ -175,24 +200,61 @@ __global__ __launch_bounds__(256) void mx_keys_kernel(const uint64_t* __restrict
   }
 }
 
+// ---- the column rules (matrix_core.hpp) ------------------------------------------
+// A rule gives, for the sorted entry i < ne, flags(K, i, ne) -- both flags of
+// the column rule packed, for the sum -- and id(K, sums, i, ne), the entry's
+// column id or kNoColumn.
+struct PlainRule {
+  __device__ uint64_t flags(const uint64_t* K, uint32_t i, uint32_t ne) const { return matrix::column_flags(K, i, ne); }
+  __device__ uint32_t id(const uint64_t* K, const uint64_t* sums, uint32_t i, uint32_t ne) const {
+    return matrix::in_column(K, i, ne) ? matrix::column_id(sums[i]) : kNoColumn;
+  }
+};
+// the border form: the run of entry i is a border column's when its first
+// entry (the lowest slot of the run) lies at a new position (start1[i] >= 1:
+// entry 0 opens a run)
+struct BorderRule {
+  const uint32_t* slot_of;
+  const uint32_t* start1;
+  uint32_t s, n_new;
+  __device__ bool kept(uint32_t i) const { return matrix::border_column_kept(slot_of[start1[i] - 1] / s, n_new); }
+  __device__ uint64_t flags(const uint64_t* K, uint32_t i, uint32_t ne) const {
+    return kept(i) ? matrix::column_flags(K, i, ne) : 0ull;
+  }
+  __device__ uint32_t id(const uint64_t* K, const uint64_t* sums, uint32_t i, uint32_t ne) const {
+    return matrix::in_column(K, i, ne) && kept(i) ? matrix::column_id(sums[i]) : kNoColumn;
+  }
+};
+// the grouped form: entries sorted by (group, hash), ids local to the group (seg[g] the group's first entry)
+struct GroupRule {
+  const uint32_t* grp;
+  const uint32_t* seg;
+  __device__ uint64_t flags(const uint64_t* K, uint32_t i, uint32_t ne) const { return matrix::column_flags(K, grp, i, ne); }
+  __device__ uint32_t id(const uint64_t* K, const uint64_t* sums, uint32_t i, uint32_t ne) const {
+    return matrix::in_column(K, grp, i, ne) ? matrix::column_id(sums[i]) - matrix::group_first_id(sums, seg[grp[i]])
+                                            : kNoColumn;
+  }
+};
+
+template <class Rule>
 __global__ __launch_bounds__(256) void mx_flags_kernel(const uint64_t* __restrict__ K, uint32_t N,
-                                                       const uint32_t* __restrict__ pos_off, uint32_t m,
+                                                       const uint32_t* __restrict__ pos_off, uint32_t m, Rule rule,
                                                        uint64_t* __restrict__ flags) {
   const uint32_t ne = pos_off[m];
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
-    flags[i] = i < ne ? matrix::column_flags(K, i, ne) : 0ull;
+    flags[i] = i < ne ? rule.flags(K, i, ne) : 0ull;
 }
 
+template <class Rule>
 __global__ __launch_bounds__(256) void mx_ids_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ slot_of,
                                                      const uint64_t* __restrict__ sums,
-                                                     const uint32_t* __restrict__ pos_off, uint32_t m,
+                                                     const uint32_t* __restrict__ pos_off, uint32_t m, Rule rule,
                                                      uint32_t* __restrict__ id_of) {
   const uint32_t ne = pos_off[m];
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256)
-    id_of[slot_of[i]] = matrix::in_column(K, i, ne) ? matrix::column_id(sums[i]) : kNoColumn;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256) id_of[slot_of[i]] = rule.id(K, sums, i, ne);
 }
 
-// ---- the border column rule (matrix_core.hpp, the border form) -----------------
+// ---- the border form's own kernels (matrix_core.hpp, the border form) ------------
 // the border's positions as a row list: the new rows first
 __global__ __launch_bounds__(256) void mxb_rows_kernel(uint32_t n, uint32_t n_old, uint32_t* __restrict__ rows) {
   for (uint32_t a = blockIdx.x * 256 + threadIdx.x; a < n; a += gridDim.x * 256)
@@ -209,33 +271,52 @@ __global__ __launch_bounds__(256) void mxb_starts_kernel(const uint64_t* __restr
     start1[i] = i < ne && (i == 0 || K[i] != K[i - 1]) ? i + 1 : 0u;
 }
 
-// the run of entry i < ne is a border column's: its first entry (the lowest
-// slot of the run) lies at a new position (start1[i] >= 1: entry 0 opens a run)
-__device__ __forceinline__ bool mxb_kept(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ start1,
-                                         uint32_t i, uint32_t s, uint32_t n_new) {
-  return matrix::border_column_kept(slot_of[start1[i] - 1] / s, n_new);
+// ---- the grouped form's own kernels (matrix_core.hpp, groups) ---------------------
+// seg[g] the first sorted entry of group g, seg[n_groups] the number of entries
+__global__ __launch_bounds__(256) void mxg_segments_kernel(const uint32_t* __restrict__ offsets, uint32_t n_groups,
+                                                           const uint32_t* __restrict__ pos_off,
+                                                           uint32_t* __restrict__ seg) {
+  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g <= n_groups; g += gridDim.x * 256) seg[g] = pos_off[offsets[g]];
 }
 
-__global__ __launch_bounds__(256) void mxb_flags_kernel(const uint64_t* __restrict__ K,
-                                                        const uint32_t* __restrict__ slot_of,
-                                                        const uint32_t* __restrict__ start1, uint32_t N,
-                                                        const uint32_t* __restrict__ pos_off, uint32_t m, uint32_t s,
-                                                        uint32_t n_new, uint64_t* __restrict__ flags) {
-  const uint32_t ne = pos_off[m];
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
-    flags[i] = i < ne && mxb_kept(slot_of, start1, i, s, n_new) ? matrix::column_flags(K, i, ne) : 0ull;
+// the group of every hash-sorted entry from its slot (the padding: n_groups, behind every group)
+__global__ __launch_bounds__(256) void mxg_entry_groups_kernel(const uint32_t* __restrict__ slot_of, uint32_t N,
+                                                               uint32_t s, const uint32_t* __restrict__ pos_grp,
+                                                               uint32_t n_groups, uint32_t* __restrict__ grp) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+    const uint32_t slot = slot_of[i];
+    grp[i] = slot == kNoColumn ? n_groups : pos_grp[slot / s];
+  }
 }
 
-__global__ __launch_bounds__(256) void mxb_ids_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ slot_of,
-                                                      const uint32_t* __restrict__ start1,
-                                                      const uint64_t* __restrict__ sums,
-                                                      const uint32_t* __restrict__ pos_off, uint32_t m, uint32_t s,
-                                                      uint32_t n_new, uint32_t* __restrict__ id_of) {
-  const uint32_t ne = pos_off[m];
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256)
-    id_of[slot_of[i]] = matrix::in_column(K, i, ne) && mxb_kept(slot_of, start1, i, s, n_new)
-                            ? matrix::column_id(sums[i])
-                            : kNoColumn;
+// the hash of every entry from its slot, after the stable sort on the group
+__global__ __launch_bounds__(256) void mxg_gather_kernel(const uint64_t* __restrict__ sk, uint32_t s,
+                                                         const uint32_t* __restrict__ pos_row,
+                                                         const uint32_t* __restrict__ slot_of,
+                                                         const uint32_t* __restrict__ pos_off, uint32_t P,
+                                                         uint64_t* __restrict__ K) {
+  const uint32_t ne = pos_off[P];
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256) {
+    const uint32_t slot = slot_of[i], p = slot / s;
+    K[i] = sk[(uint64_t)pos_row[p] * s + (slot - p * s)];
+  }
+}
+
+// a group of one position: its cell is the diagonal rule's
+__global__ __launch_bounds__(256) void mxg_single_kernel(const uint32_t* __restrict__ offsets,
+                                                         const uint64_t* __restrict__ cell_off, uint32_t n_groups,
+                                                         const uint32_t* __restrict__ pos_len,
+                                                         uint32_t* __restrict__ common, uint32_t* __restrict__ total,
+                                                         float* __restrict__ ani) {
+  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n_groups; g += gridDim.x * 256) {
+    const uint32_t p = offsets[g];
+    if (offsets[g + 1] - p != 1) continue;
+    const uint32_t len = pos_len[p];
+    const uint64_t cell = cell_off[g];
+    if (common) common[cell] = len;
+    if (total) total[cell] = len;
+    if (ani) ani[cell] = len ? 1.0f : 0.0f;
+  }
 }
 
 // piece[a * s ..) the ids of position a's entries that lie in a column, in the row's order; piece_cnt[a]
@@ -519,27 +600,63 @@ __global__ __launch_bounds__(256) void mx_common_kernel(L a) {
   }
 }
 
+uint32_t bits_for(uint32_t values) {  // the bits that hold 0 .. values - 1
+  uint32_t b = 1;
+  while (b < 32 && (1ull << b) < values) ++b;
+  return b;
+}
+
+// flags, their inclusive sum and the ids of the sorted entries by one column rule
+template <class Rule>
+hipError_t columns_by(const Rule& rule, const uint64_t* K, const uint32_t* slot_of, uint32_t N, const uint32_t* pos_off,
+                      uint32_t m, uint64_t* flags, uint64_t* sums, uint32_t* id_of, void* tmp, size_t tmp_bytes,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(mx_flags_kernel<Rule>, grid_for(N), dim3(256), 0, st, K, N, pos_off, m, rule, flags);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, (const uint64_t*)flags, sums, (int)N, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(mx_ids_kernel<Rule>, grid_for(N), dim3(256), 0, st, K, slot_of, sums, pos_off, m, rule, id_of);
+  return hipGetLastError();
+}
+
 }  // namespace
 
-// The positions part of a call, up to the one read-back before the product:
-// pos_row / pos_len / piece / piece_cnt in context scratch and the three counts.
-// m s < 2^31 (the caller's check).  m <= kMaxRows: mx_offsets_kernel; more rows
-// (the pair form only): mxp_positions_kernel and a scan.  Synchronises st.
-// border_n_old != kNoBorder: the border form of m == n rows -- d_rows is not
-// read, the positions are the border's, the columns by the border column rule,
-// and new_entries is counted; every other caller takes the path it took before.
+// The positions part of every form, up to the one read-back before the
+// product: pos_row / pos_len / piece / piece_cnt in context scratch and the
+// counts.  m s < 2^31 (the caller's check).  Synchronises st.  The form selects
+// three things, everything else is one sequence:
+//   the positions and their offsets -- kRows at m <= kMaxRows: mx_offsets_kernel;
+//     more rows (the pair and border forms), and kGroups always:
+//     mx_positions_kernel and a scan; kBorder (m == n >= n_old, the caller's
+//     check; d_rows is not read): the border's positions as a row list first;
+//     kGroups: every group's first entry (mxg_segments_kernel);
+//   kGroups with two groups or more: after the 64-bit sort a stable sort of
+//     (group, slot) on the group's bits and a gather of the hashes (a segmented
+//     sort over the groups' entry ranges was measured and dropped, DESIGN.md
+//     4.11); one group: the group words are cleared;
+//   the column rule -- plain, the border's (mxb_starts_kernel and an inclusive
+//     max give every sorted entry the first entry of its run; new_entries is
+//     counted) or the group's (ids local to a group).
 gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st, uint32_t border_n_old) {
-  const uint32_t s = c->s;
+                         const uint32_t* d_rows, uint32_t m, const MatrixForm& form, MatrixPrep* out, hipStream_t st) {
+  const uint32_t s = c->s, G = form.n_groups;
   const uint32_t N = (uint32_t)((uint64_t)m * s);
-  const bool border = border_n_old != kNoBorder;
-  const uint32_t n_new = border ? n - border_n_old : 0u;  // (border: m == n >= border_n_old, the caller's check)
-  uint32_t *pos_row, *pos_len, *pos_off, *vals_in, *vals_out, *piece, *piece_cnt;
+  const bool border = form.kind == MatrixForm::kBorder, groups = form.kind == MatrixForm::kGroups;
+  const uint32_t n_new = border ? n - form.n_old : 0u;
+  uint32_t *pos_row, *pos_len, *pos_off, *vals_in, *vals_out, *piece, *piece_cnt, *pos_grp = nullptr;
   uint64_t *keys_in, *keys_out, *sums, *h_back;
-  GG_HIP(c, scratch_t(c, "mx_pos", (size_t)4 * m + 1, &pos_row));
-  pos_len = pos_row + m;
-  piece_cnt = pos_len + m;
-  pos_off = piece_cnt + m;
+  if (groups) {  // m + 1 words each: pos_len is scanned in place
+    GG_HIP(c, scratch_t(c, "mxg_pos", (size_t)5 * (m + 1), &pos_row));
+    pos_len = pos_row + (m + 1);
+    pos_grp = pos_len + (m + 1);
+    pos_off = pos_grp + (m + 1);
+    piece_cnt = pos_off + (m + 1);
+  } else {
+    GG_HIP(c, scratch_t(c, "mx_pos", (size_t)4 * m + 1, &pos_row));
+    pos_len = pos_row + m;
+    piece_cnt = pos_len + m;
+    pos_off = piece_cnt + m;
+  }
   GG_HIP(c, scratch_t(c, "mx_keys_in", (size_t)N, &keys_in));
   GG_HIP(c, scratch_t(c, "mx_keys_out", (size_t)N, &keys_out));
   GG_HIP(c, scratch_t(c, "mx_sums", (size_t)N, &sums));
@@ -547,13 +664,22 @@ gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const
   GG_HIP(c, scratch_t(c, "mx_vals_out", (size_t)N, &vals_out));
   GG_HIP(c, scratch_t(c, "mx_piece", (size_t)N, &piece));
   GG_HIP(c, host_scratch_t(c, "mx_back", 3, &h_back));
-  size_t sort_bytes = 0, scan_bytes = 0, off_bytes = 0, max_bytes = 0, red_bytes = 0;
+  const bool scanned = groups || m > matrix::kMaxRows;  // the offsets by mx_positions_kernel and a scan
+  const int group_bits = (int)bits_for(G + 1);
+  size_t sort_bytes = 0, sort2_bytes = 0, scan_bytes = 0, off_bytes = 0, max_bytes = 0, red_bytes = 0;
   GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
                                                (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, 64));
   GG_HIP(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N));
-  if (m > matrix::kMaxRows)
+  if (scanned)
     GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, off_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                (int)(m + 1)));
+  uint32_t *grp_in = nullptr, *grp_out = nullptr;  // (groups) the group of every entry, before and after the second sort
+  if (groups) {
+    GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort2_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                 (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, group_bits));
+    GG_HIP(c, scratch_t(c, "mxg_grp_in", (size_t)N, &grp_in));
+    GG_HIP(c, scratch_t(c, "mxg_grp_out", (size_t)N, &grp_out));
+  }
   uint32_t *b_rows = nullptr, *b_new = nullptr;  // (the border) the row list; the new positions' kept entries
   if (border) {
     GG_HIP(c, hipcub::DeviceScan::InclusiveScan(nullptr, max_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
@@ -562,58 +688,75 @@ gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const
     GG_HIP(c, scratch_t(c, "mxb_rows", (size_t)m + 1, &b_rows));
     b_new = b_rows + m;
   }
-  const size_t tmp_bytes = std::max(std::max(std::max(sort_bytes, scan_bytes), off_bytes), std::max(max_bytes, red_bytes));
+  const size_t tmp_bytes = std::max({sort_bytes, sort2_bytes, scan_bytes, off_bytes, max_bytes, red_bytes});
   uint8_t* tmp;
   GG_HIP(c, scratch_t(c, "mx_tmp", std::max<size_t>(tmp_bytes, 1), &tmp));
 
   size_t bytes = tmp_bytes;
   if (border) {
-    hipLaunchKernelGGL(mxb_rows_kernel, grid_for(m), dim3(256), 0, st, n, border_n_old, b_rows);
+    hipLaunchKernelGGL(mxb_rows_kernel, grid_for(m), dim3(256), 0, st, n, form.n_old, b_rows);
     GG_HIP(c, hipGetLastError());
     d_rows = b_rows;
   }
-  if (m <= matrix::kMaxRows) {
+  if (!scanned) {
     hipLaunchKernelGGL(mx_offsets_kernel, dim3(1), dim3(kOffBlock), 0, st, d_lens, n, s, d_rows, m, pos_row, pos_len,
                        pos_off);
     GG_HIP(c, hipGetLastError());
   } else {
-    uint32_t* len1;  // the m lengths and a 0 behind them: the scan's last item is the number of entries
-    GG_HIP(c, scratch_t(c, "mxp_len1", (size_t)m + 1, &len1));
-    hipLaunchKernelGGL(mxp_positions_kernel, grid_for((uint64_t)m + 1), dim3(256), 0, st, d_lens, n, s, d_rows, m,
-                       pos_row, pos_len, len1);
+    uint32_t* len1 = pos_len;  // the m lengths and a 0 behind them: the scan's last item is the number of entries
+    if (groups) {
+      hipLaunchKernelGGL(mx_positions_kernel<true>, grid_for((uint64_t)m + 1), dim3(256), 0, st, d_lens, n, s, d_rows, m,
+                         pos_row, pos_len, len1, form.d_offsets, G, pos_grp);
+    } else {
+      GG_HIP(c, scratch_t(c, "mxp_len1", (size_t)m + 1, &len1));
+      hipLaunchKernelGGL(mx_positions_kernel<false>, grid_for((uint64_t)m + 1), dim3(256), 0, st, d_lens, n, s, d_rows, m,
+                         pos_row, pos_len, len1, nullptr, 0u, nullptr);
+    }
     GG_HIP(c, hipGetLastError());
     GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)len1, pos_off, (int)(m + 1), st));
+  }
+  if (groups) {
+    hipLaunchKernelGGL(mxg_segments_kernel, grid_for((uint64_t)G + 1), dim3(256), 0, st, form.d_offsets, G, pos_off,
+                       form.d_seg);
+    GG_HIP(c, hipGetLastError());
   }
   hipLaunchKernelGGL(mx_keys_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, m, pos_row, pos_len, pos_off, keys_in,
                      vals_in);
   GG_HIP(c, hipGetLastError());
+  // K, slot_of: the sorted entries; everything from the number of entries on is padding
+  uint64_t* K = keys_out;
+  uint32_t* slot_of = vals_out;
   bytes = tmp_bytes;
   GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
                                                vals_out, (int)N, 0, 64, st));
-  uint64_t* flags = keys_in;  // (the sort's input is free)
-  uint32_t* id_of = vals_in;
+  if (groups && G > 1) {  // by (group, hash)
+    hipLaunchKernelGGL(mxg_entry_groups_kernel, grid_for(N), dim3(256), 0, st, vals_out, N, s, pos_grp, G, grp_in);
+    GG_HIP(c, hipGetLastError());
+    bytes = tmp_bytes;
+    GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint32_t*)grp_in, grp_out, (const uint32_t*)vals_out,
+                                                 vals_in, (int)N, 0, group_bits, st));
+    slot_of = vals_in;
+    K = keys_in;
+    hipLaunchKernelGGL(mxg_gather_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, pos_row, slot_of, pos_off, m, K);
+    GG_HIP(c, hipGetLastError());
+  } else if (groups) {
+    GG_HIP(c, hipMemsetAsync(grp_out, 0, (size_t)N * sizeof(uint32_t), st));
+  }
+  uint64_t* flags = K == keys_out ? keys_in : keys_out;  // (the buffer the sorted keys are not in)
+  uint32_t* id_of = slot_of == vals_out ? vals_in : vals_out;
+  bytes = tmp_bytes;
   if (border) {
     // every entry's run start: the two u32 arrays that are free until the ids (vals_in) and the pieces are written
     uint32_t *start_in = vals_in, *start1 = piece;
-    hipLaunchKernelGGL(mxb_starts_kernel, grid_for(N), dim3(256), 0, st, keys_out, N, pos_off, m, start_in);
+    hipLaunchKernelGGL(mxb_starts_kernel, grid_for(N), dim3(256), 0, st, K, N, pos_off, m, start_in);
     GG_HIP(c, hipGetLastError());
-    bytes = tmp_bytes;
     GG_HIP(c, hipcub::DeviceScan::InclusiveScan(tmp, bytes, (const uint32_t*)start_in, start1, hipcub::Max(), (int)N, st));
-    hipLaunchKernelGGL(mxb_flags_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, start1, N, pos_off, m, s,
-                       n_new, flags);
-    GG_HIP(c, hipGetLastError());
-    bytes = tmp_bytes;
-    GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
-    hipLaunchKernelGGL(mxb_ids_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, start1, sums, pos_off, m, s,
-                       n_new, id_of);
-    GG_HIP(c, hipGetLastError());
+    GG_HIP(c, columns_by(BorderRule{slot_of, start1, s, n_new}, K, slot_of, N, pos_off, m, flags, sums, id_of, tmp,
+                         tmp_bytes, st));
+  } else if (groups) {
+    GG_HIP(c, columns_by(GroupRule{grp_out, form.d_seg}, K, slot_of, N, pos_off, m, flags, sums, id_of, tmp, tmp_bytes, st));
   } else {
-    hipLaunchKernelGGL(mx_flags_kernel, grid_for(N), dim3(256), 0, st, keys_out, N, pos_off, m, flags);
-    GG_HIP(c, hipGetLastError());
-    bytes = tmp_bytes;
-    GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
-    hipLaunchKernelGGL(mx_ids_kernel, grid_for(N), dim3(256), 0, st, keys_out, vals_out, sums, pos_off, m, id_of);
-    GG_HIP(c, hipGetLastError());
+    GG_HIP(c, columns_by(PlainRule{}, K, slot_of, N, pos_off, m, flags, sums, id_of, tmp, tmp_bytes, st));
   }
   hipLaunchKernelGGL(mx_pieces_kernel, dim3(m), dim3(256), 0, st, id_of, pos_len, s, piece, piece_cnt);
   GG_HIP(c, hipGetLastError());
@@ -637,225 +780,141 @@ gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const
   return GG_OK;
 }
 
-gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
-                            uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
-                            hipStream_t st) {
-  if (sum) *sum = gg_matrix_summary{};
-  if (m == 0) return GG_OK;
-  const uint32_t s = c->s;
-  if ((uint64_t)m * s >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, "gg_ani_matrix: 2^31 sketch slots or more");
-  MatrixPrep prep;
-  const gg_status ps = matrix_prepare(c, "gg_ani_matrix", d_sk, d_lens, n, d_rows, m, &prep, st);
-  if (ps != GG_OK) return ps;
-  const uint32_t *pos_row = prep.pos_row, *pos_len = prep.pos_len, *piece = prep.piece, *piece_cnt = prep.piece_cnt;
-  const uint64_t n_entries = prep.n_entries, n_columns = prep.n_columns, column_entries = prep.column_entries;
+namespace {
 
-  MxLaunch a{d_sk, s, m, pos_row, pos_len, piece, piece_cnt, d_common, d_total, d_ani, c->k, 0.0, nullptr, 0, nullptr};
-  const dim3 grid(matrix::tile_pairs_of(matrix::tiles_of(m)));
+// the fields every form's launch takes from the context and the positions part
+template <class L>
+L launch_of(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p) {
+  L a{};
+  a.sk = d_sk;
+  a.s = c->s;
+  a.m = p.m;
+  a.pos_row = p.pos_row;
+  a.pos_len = p.pos_len;
+  a.piece = p.piece;
+  a.piece_cnt = p.piece_cnt;
+  a.k = c->k;
+  return a;
+}
+
+// The dense product of tile_pairs workgroups over `cells` cells and the
+// summary: with d_ani by ani_flagged_passes (mirror_m: its patch mirrors a
+// flagged cell of one [m x m] matrix; cells_per_flagged the cells a listed
+// entry stands for), else a plain launch.  Synchronises st.
+template <class L>
+gg_status dense_product(gg_ctx* c, const char* who, L a, uint32_t tile_pairs, uint64_t cells, uint32_t mirror_m,
+                        uint64_t cells_per_flagged, const MatrixPrep& p, gg_matrix_summary* sum, hipStream_t st) {
+  const dim3 grid(tile_pairs);
   uint64_t flagged = 0;
-  if (d_ani) {
+  if (tile_pairs && a.ani) {
     const gg_status r = ani_flagged_passes(
-        c, "gg_ani_matrix", (uint64_t)m * m,
+        c, who, cells,
         [&](double E, AniFlagged* list, uint64_t cap, unsigned long long* count) {
           a.E = E;
           a.list = list;
           a.cap = cap;
           a.count = count;
-          hipLaunchKernelGGL(mx_common_kernel<MxLaunch>, grid, dim3(256), 0, st, a);
+          hipLaunchKernelGGL(mx_common_kernel<L>, grid, dim3(256), 0, st, a);
           return hipGetLastError();
         },
-        d_ani, nullptr, m, &flagged, st);
+        a.ani, nullptr, mirror_m, &flagged, st);
     if (r != GG_OK) return r;
   } else {
-    hipLaunchKernelGGL(mx_common_kernel<MxLaunch>, grid, dim3(256), 0, st, a);
-    GG_HIP(c, hipGetLastError());
+    if (tile_pairs) {
+      hipLaunchKernelGGL(mx_common_kernel<L>, grid, dim3(256), 0, st, a);
+      GG_HIP(c, hipGetLastError());
+    }
     GG_HIP(c, hipStreamSynchronize(st));
   }
   if (sum) {
-    sum->n_entries = n_entries;
-    sum->n_columns = n_columns;
-    sum->column_entries = column_entries;
-    sum->ani_rechecked = 2 * flagged;  // cells: the matrix mirrors each listed entry
+    sum->n_entries = p.n_entries;
+    sum->n_columns = p.n_columns;
+    sum->column_entries = p.column_entries;
+    sum->ani_rechecked = cells_per_flagged * flagged;
   }
   return GG_OK;
+}
+
+// The pair and border forms' launch over prepared positions (cmin / sufmin:
+// ensure_cmin's tables on the device) and its launches: one takes fewer than
+// 2^32 threads, 2^24 workgroups of 256, so the tile pairs (< 2^31: the limits
+// of the form) go in slices of kPairSlice, in stream order.
+template <class L>
+L pair_launch_of(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, const uint32_t* d_cmin, const uint32_t* d_sufmin,
+                 gg_pair* d_out, uint64_t cap, uint64_t* d_count) {
+  L a = launch_of<L>(c, d_sk, p);
+  a.count = (unsigned long long*)d_count;
+  a.cmin = d_cmin;
+  a.sufmin = d_sufmin;
+  a.tmax = 2 * c->s;
+  a.zero_passes = c->sufmin_host[0] == 0;
+  a.out = d_out;
+  a.out_cap = cap;
+  return a;
+}
+
+template <class L>
+gg_status launch_pair_slices(gg_ctx* c, L a, uint32_t tile_pairs, hipStream_t st) {
+  const uint32_t slice = test_pair_slice();
+  for (uint32_t base = 0; base < tile_pairs; base += std::min(slice, tile_pairs - base)) {
+    a.wg_base = base;
+    hipLaunchKernelGGL(mx_common_kernel<L>, dim3(std::min(slice, tile_pairs - base)), dim3(256), 0, st, a);
+    GG_HIP(c, hipGetLastError());
+  }
+  return GG_OK;
+}
+
+}  // namespace
+
+gg_status ani_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
+                            uint32_t m, uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
+                            hipStream_t st) {
+  if (sum) *sum = gg_matrix_summary{};
+  if (m == 0) return GG_OK;
+  if ((uint64_t)m * c->s >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, "gg_ani_matrix: 2^31 sketch slots or more");
+  MatrixPrep prep;
+  const gg_status ps = matrix_prepare(c, "gg_ani_matrix", d_sk, d_lens, n, d_rows, m, MatrixForm{}, &prep, st);
+  if (ps != GG_OK) return ps;
+  MxLaunch a = launch_of<MxLaunch>(c, d_sk, prep);
+  a.common = d_common;
+  a.total = d_total;
+  a.ani = d_ani;
+  // (ani_rechecked counts cells: the matrix mirrors each listed entry)
+  return dense_product(c, "gg_ani_matrix", a, matrix::tile_pairs_of(matrix::tiles_of(m)), (uint64_t)m * m, m, 2, prep, sum,
+                       st);
 }
 
 // ---- the pair form ------------------------------------------
 // The product over prepared positions with the thresholded epilogue: the
 // passing pairs appended to d_out (unsorted), *d_count grown by the number
-// found, nothing written past cap.  cmin / sufmin: ensure_cmin's tables on the
-// device.  Asynchronous.
+// found, nothing written past cap.  Asynchronous.
 gg_status pairs_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, const uint32_t* d_cmin,
                               const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
                               hipStream_t st) {
   if (p.m < 2) return GG_OK;
-  MxPairLaunch a{};
-  a.sk = d_sk;
-  a.s = c->s;
-  a.m = p.m;
-  a.pos_row = p.pos_row;
-  a.pos_len = p.pos_len;
-  a.piece = p.piece;
-  a.piece_cnt = p.piece_cnt;
-  a.k = c->k;
-  a.count = (unsigned long long*)d_count;
-  a.cmin = d_cmin;
-  a.sufmin = d_sufmin;
-  a.tmax = 2 * c->s;
-  a.zero_passes = c->sufmin_host[0] == 0;
-  a.out = d_out;
-  a.out_cap = cap;
-  // One launch takes fewer than 2^32 threads, 2^24 workgroups of 256: the tile
-  // pairs (< 2^31: pair_limits_ok) go in slices of kPairSlice, in stream order.
-  const uint32_t tile_pairs = matrix::tile_pairs_of(matrix::tiles_of(p.m));
-  const uint32_t slice = test_pair_slice();
-  for (uint32_t base = 0; base < tile_pairs; base += std::min(slice, tile_pairs - base)) {
-    a.wg_base = base;
-    hipLaunchKernelGGL(mx_common_kernel<MxPairLaunch>, dim3(std::min(slice, tile_pairs - base)), dim3(256), 0, st, a);
-    GG_HIP(c, hipGetLastError());
-  }
-  return GG_OK;
+  return launch_pair_slices(c, pair_launch_of<MxPairLaunch>(c, d_sk, p, d_cmin, d_sufmin, d_out, cap, d_count),
+                            matrix::tile_pairs_of(matrix::tiles_of(p.m)), st);
 }
 
 // ---- the border form ----------------------------------------
-// The same over positions prepared with border_n_old = n - n_new: the border
-// tile pairs in slices, the cells of a new position only.  Asynchronous.
+// The same over positions prepared as a border of n_old = p.m - n_new: the
+// border tile pairs in slices, the cells of a new position only.  Asynchronous.
 gg_status pairs_border_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, uint32_t n_new,
                                      const uint32_t* d_cmin, const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap,
                                      uint64_t* d_count, hipStream_t st) {
   if (p.m < 2 || n_new == 0) return GG_OK;
-  MxBorderLaunch a{};
-  a.sk = d_sk;
-  a.s = c->s;
-  a.m = p.m;
-  a.pos_row = p.pos_row;
-  a.pos_len = p.pos_len;
-  a.piece = p.piece;
-  a.piece_cnt = p.piece_cnt;
-  a.k = c->k;
-  a.count = (unsigned long long*)d_count;
-  a.cmin = d_cmin;
-  a.sufmin = d_sufmin;
-  a.tmax = 2 * c->s;
-  a.zero_passes = c->sufmin_host[0] == 0;
-  a.out = d_out;
-  a.out_cap = cap;
+  MxBorderLaunch a = pair_launch_of<MxBorderLaunch>(c, d_sk, p, d_cmin, d_sufmin, d_out, cap, d_count);
   a.n_new = n_new;
   a.tiles_new = matrix::tiles_of(n_new);
-  const uint32_t tile_pairs = matrix::border_tile_pairs(a.tiles_new, matrix::tiles_of(p.m));  // (< 2^31: border_limits_ok)
-  const uint32_t slice = test_pair_slice();
-  for (uint32_t base = 0; base < tile_pairs; base += std::min(slice, tile_pairs - base)) {
-    a.wg_base = base;
-    hipLaunchKernelGGL(mx_common_kernel<MxBorderLaunch>, dim3(std::min(slice, tile_pairs - base)), dim3(256), 0, st, a);
-    GG_HIP(c, hipGetLastError());
-  }
-  return GG_OK;
+  return launch_pair_slices(c, a, matrix::border_tile_pairs(a.tiles_new, matrix::tiles_of(p.m)), st);
 }
 
 // ---- the matrices of many groups in one call ----------------
-//   mxg_positions_kernel  every position's group (a search of offsets), row
-//                         and length, for any number of positions;
-//   hipcub ExclusiveSum   the positions' first entries; mxg_segments_kernel
-//                         every group's first entry;
-//   mx_keys_kernel        as above, over all P positions;
-//   the sort by (group, hash): the 64-bit sort above, then a stable sort of
-//                         (group, slot) on the group's bits and a gather of
-//                         the hashes; one group needs the first only
-//                         (a segmented sort over the groups' entry ranges was
-//                         measured and dropped);
-//   mxg_entry_groups_kernel, mxg_flags_kernel, InclusiveSum, mxg_ids_kernel:
-//                         the grouped column rule, ids local to the group;
-//   mx_pieces_kernel      unchanged;
+// The layout on the host (offsets arrive from it, and it shapes the launches),
+// the positions part in its grouped form, then
 //   mxg_single_kernel     the one cell of every group of one position;
 //   mx_common_kernel<MxGroupLaunch>  the groups of two positions or more.
 namespace {
-
-__global__ __launch_bounds__(256) void mxg_positions_kernel(const uint32_t* __restrict__ lens, uint32_t n, uint32_t s,
-                                                            const uint32_t* __restrict__ members,
-                                                            const uint32_t* __restrict__ offsets, uint32_t n_groups,
-                                                            uint32_t P, uint32_t* __restrict__ pos_row,
-                                                            uint32_t* __restrict__ pos_len,
-                                                            uint32_t* __restrict__ pos_grp) {
-  for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p <= P; p += gridDim.x * 256) {
-    if (p == P) {  // (the scan's last item: its exclusive sum is the number of entries)
-      pos_len[p] = 0;
-      continue;
-    }
-    const uint32_t g = members[p];
-    const bool ok = g < n;
-    pos_row[p] = ok ? g : kNoRow;
-    pos_len[p] = ok ? min(lens[g], s) : 0u;
-    pos_grp[p] = matrix::group_of_position(offsets, n_groups, p);
-  }
-}
-
-// seg[g] the first sorted entry of group g, seg[n_groups] the number of entries
-__global__ __launch_bounds__(256) void mxg_segments_kernel(const uint32_t* __restrict__ offsets, uint32_t n_groups,
-                                                           const uint32_t* __restrict__ pos_off,
-                                                           uint32_t* __restrict__ seg) {
-  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g <= n_groups; g += gridDim.x * 256) seg[g] = pos_off[offsets[g]];
-}
-
-// the group of every hash-sorted entry from its slot (the padding: n_groups, behind every group)
-__global__ __launch_bounds__(256) void mxg_entry_groups_kernel(const uint32_t* __restrict__ slot_of, uint32_t N,
-                                                               uint32_t s, const uint32_t* __restrict__ pos_grp,
-                                                               uint32_t n_groups, uint32_t* __restrict__ grp) {
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
-    const uint32_t slot = slot_of[i];
-    grp[i] = slot == kNoColumn ? n_groups : pos_grp[slot / s];
-  }
-}
-
-// the hash of every entry from its slot, after the stable sort on the group
-__global__ __launch_bounds__(256) void mxg_gather_kernel(const uint64_t* __restrict__ sk, uint32_t s,
-                                                         const uint32_t* __restrict__ pos_row,
-                                                         const uint32_t* __restrict__ slot_of,
-                                                         const uint32_t* __restrict__ pos_off, uint32_t P,
-                                                         uint64_t* __restrict__ K) {
-  const uint32_t ne = pos_off[P];
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256) {
-    const uint32_t slot = slot_of[i], p = slot / s;
-    K[i] = sk[(uint64_t)pos_row[p] * s + (slot - p * s)];
-  }
-}
-
-__global__ __launch_bounds__(256) void mxg_flags_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ grp,
-                                                        uint32_t N, const uint32_t* __restrict__ pos_off, uint32_t P,
-                                                        uint64_t* __restrict__ flags) {
-  const uint32_t ne = pos_off[P];
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256)
-    flags[i] = i < ne ? matrix::column_flags(K, grp, i, ne) : 0ull;
-}
-
-__global__ __launch_bounds__(256) void mxg_ids_kernel(const uint64_t* __restrict__ K, const uint32_t* __restrict__ grp,
-                                                      const uint32_t* __restrict__ slot_of,
-                                                      const uint64_t* __restrict__ sums,
-                                                      const uint32_t* __restrict__ seg,
-                                                      const uint32_t* __restrict__ pos_off, uint32_t P,
-                                                      uint32_t* __restrict__ id_of) {
-  const uint32_t ne = pos_off[P];
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < ne; i += gridDim.x * 256)
-    id_of[slot_of[i]] = matrix::in_column(K, grp, i, ne)
-                            ? matrix::column_id(sums[i]) - matrix::group_first_id(sums, seg[grp[i]])
-                            : kNoColumn;
-}
-
-// a group of one position: its cell is the diagonal rule's
-__global__ __launch_bounds__(256) void mxg_single_kernel(const uint32_t* __restrict__ offsets,
-                                                         const uint64_t* __restrict__ cell_off, uint32_t n_groups,
-                                                         const uint32_t* __restrict__ pos_len,
-                                                         uint32_t* __restrict__ common, uint32_t* __restrict__ total,
-                                                         float* __restrict__ ani) {
-  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n_groups; g += gridDim.x * 256) {
-    const uint32_t p = offsets[g];
-    if (offsets[g + 1] - p != 1) continue;
-    const uint32_t len = pos_len[p];
-    const uint64_t cell = cell_off[g];
-    if (common) common[cell] = len;
-    if (total) total[cell] = len;
-    if (ani) ani[cell] = len ? 1.0f : 0.0f;
-  }
-}
 
 // offsets of a grouped call (host words in every form): they begin at 0,
 // ascend and keep the limits; cell_off / tp_off (may be null) receive the layout
@@ -881,12 +940,6 @@ gg_status check_group_offsets(const std::string& w, const uint32_t* offsets, uin
   return GG_OK;
 }
 
-uint32_t bits_for(uint32_t values) {  // the bits that hold 0 .. values - 1
-  uint32_t b = 1;
-  while (b < 32 && (1ull << b) < values) ++b;
-  return b;
-}
-
 }  // namespace
 
 gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
@@ -896,298 +949,188 @@ gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32
   const char* who = "gg_ani_matrix_groups";
   if (sum) *sum = gg_matrix_summary{};
   if (n_groups == 0) return GG_OK;
-  const uint32_t s = c->s, G = n_groups;
-  // the layout on the host: offsets arrive from it, and it shapes the launches
-  uint32_t *h_off, *h_tp;
-  uint64_t* h_cell;
+  const uint32_t G = n_groups;
+  uint32_t *h_off, *h_tp, *d_off, *d_tp, *d_seg;
+  uint64_t *h_cell, *d_cell;
   GG_HIP(c, host_scratch_t(c, "mxg_h_off", (size_t)2 * (G + 1), &h_off));
   GG_HIP(c, host_scratch_t(c, "mxg_h_cell", (size_t)G + 1, &h_cell));
   h_tp = h_off + (G + 1);
   std::string err;
-  const gg_status chk = check_group_offsets(who, offsets, G, s, h_cell, h_tp, err);
+  const gg_status chk = check_group_offsets(who, offsets, G, c->s, h_cell, h_tp, err);
   if (chk != GG_OK) return fail(c, chk, err);
   const uint32_t P = offsets[G];
   if (P == 0) return GG_OK;
   memcpy(h_off, offsets, (size_t)(G + 1) * sizeof(uint32_t));
-  const uint32_t N = P * s, tile_pairs = h_tp[G];
-  const uint64_t cells = h_cell[G];
   bool singles = false;
   for (uint32_t g = 0; g < G && !singles; ++g) singles = offsets[g + 1] - offsets[g] == 1;
-
-  uint32_t *pos_row, *pos_len, *pos_grp, *pos_off, *piece_cnt, *d_off, *d_tp, *seg, *vals_in, *vals_out, *grp_in, *grp_out,
-      *piece;
-  uint64_t *d_cell, *keys_in, *keys_out, *sums, *h_back;
-  GG_HIP(c, scratch_t(c, "mxg_pos", (size_t)5 * (P + 1), &pos_row));
-  pos_len = pos_row + (P + 1);
-  pos_grp = pos_len + (P + 1);
-  pos_off = pos_grp + (P + 1);
-  piece_cnt = pos_off + (P + 1);
   GG_HIP(c, scratch_t(c, "mxg_off", (size_t)3 * (G + 1), &d_off));
   d_tp = d_off + (G + 1);
-  seg = d_tp + (G + 1);
+  d_seg = d_tp + (G + 1);
   GG_HIP(c, scratch_t(c, "mxg_cell", (size_t)G + 1, &d_cell));
-  GG_HIP(c, scratch_t(c, "mx_keys_in", (size_t)N, &keys_in));
-  GG_HIP(c, scratch_t(c, "mx_keys_out", (size_t)N, &keys_out));
-  GG_HIP(c, scratch_t(c, "mx_sums", (size_t)N, &sums));
-  GG_HIP(c, scratch_t(c, "mx_vals_in", (size_t)N, &vals_in));
-  GG_HIP(c, scratch_t(c, "mx_vals_out", (size_t)N, &vals_out));
-  GG_HIP(c, scratch_t(c, "mxg_grp_in", (size_t)N, &grp_in));
-  GG_HIP(c, scratch_t(c, "mxg_grp_out", (size_t)N, &grp_out));
-  GG_HIP(c, scratch_t(c, "mx_piece", (size_t)N, &piece));
-  GG_HIP(c, host_scratch_t(c, "mx_back", 2, &h_back));
-  const int group_bits = (int)bits_for(G + 1);
-  size_t sort_bytes = 0, sort2_bytes = 0, scan_bytes = 0, off_bytes = 0;
-  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, 64));
-  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort2_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                               (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)N, 0, group_bits));
-  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)N));
-  GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, off_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                             (int)(P + 1)));
-  const size_t tmp_bytes = std::max(std::max(sort_bytes, sort2_bytes), std::max(scan_bytes, off_bytes));
-  uint8_t* tmp;
-  GG_HIP(c, scratch_t(c, "mx_tmp", std::max<size_t>(tmp_bytes, 1), &tmp));
-
   GG_HIP(c, hipMemcpyAsync(d_off, h_off, (size_t)2 * (G + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   GG_HIP(c, hipMemcpyAsync(d_cell, h_cell, (size_t)(G + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(mxg_positions_kernel, grid_for((uint64_t)P + 1), dim3(256), 0, st, d_lens, n, s, d_members, d_off, G,
-                     P, pos_row, pos_len, pos_grp);
-  GG_HIP(c, hipGetLastError());
-  size_t bytes = tmp_bytes;
-  GG_HIP(c, hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const uint32_t*)pos_len, pos_off, (int)(P + 1), st));
-  hipLaunchKernelGGL(mxg_segments_kernel, grid_for((uint64_t)G + 1), dim3(256), 0, st, d_off, G, pos_off, seg);
-  GG_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(mx_keys_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, P, pos_row, pos_len, pos_off, keys_in,
-                     vals_in);
-  GG_HIP(c, hipGetLastError());
-  // K, slot_of, grp: the entries sorted by (group, hash); everything from the number of entries on is padding
-  uint64_t* K = keys_out;
-  uint32_t *slot_of = vals_out, *grp = grp_out;
-  bytes = tmp_bytes;
-  GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint64_t*)keys_in, keys_out, (const uint32_t*)vals_in,
-                                               vals_out, (int)N, 0, 64, st));
-  if (G > 1) {
-    hipLaunchKernelGGL(mxg_entry_groups_kernel, grid_for(N), dim3(256), 0, st, vals_out, N, s, pos_grp, G, grp_in);
-    GG_HIP(c, hipGetLastError());
-    bytes = tmp_bytes;
-    GG_HIP(c, hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint32_t*)grp_in, grp_out, (const uint32_t*)vals_out,
-                                                 vals_in, (int)N, 0, group_bits, st));
-    slot_of = vals_in;
-    K = keys_in;
-    hipLaunchKernelGGL(mxg_gather_kernel, grid_for(N), dim3(256), 0, st, d_sk, s, pos_row, slot_of, pos_off, P, K);
-    GG_HIP(c, hipGetLastError());
-  } else {
-    GG_HIP(c, hipMemsetAsync(grp, 0, (size_t)N * sizeof(uint32_t), st));
-  }
-  uint64_t* flags = K == keys_out ? keys_in : keys_out;  // (the buffer the sorted keys are not in)
-  uint32_t* id_of = slot_of == vals_out ? vals_in : vals_out;
-  hipLaunchKernelGGL(mxg_flags_kernel, grid_for(N), dim3(256), 0, st, K, grp, N, pos_off, P, flags);
-  GG_HIP(c, hipGetLastError());
-  bytes = tmp_bytes;
-  GG_HIP(c, hipcub::DeviceScan::InclusiveSum(tmp, bytes, (const uint64_t*)flags, sums, (int)N, st));
-  hipLaunchKernelGGL(mxg_ids_kernel, grid_for(N), dim3(256), 0, st, K, grp, slot_of, sums, seg, pos_off, P, id_of);
-  GG_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(mx_pieces_kernel, dim3(P), dim3(256), 0, st, id_of, pos_len, s, piece, piece_cnt);
-  GG_HIP(c, hipGetLastError());
-  // entries, columns, column entries: the one read-back before the product
-  // (the tile pairs' total is the host's: offsets came from it)
-  GG_HIP(c, hipMemcpyAsync(&h_back[0], sums + (N - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  GG_HIP(c, hipMemcpyAsync(&h_back[1], pos_off + P, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  GG_HIP(c, hipStreamSynchronize(st));
-  const uint64_t n_columns = (uint32_t)h_back[0], column_entries = h_back[0] >> 32, n_entries = (uint32_t)h_back[1];
-  if (n_entries > N || column_entries > n_entries || 2 * n_columns > column_entries)
-    return fail(c, GG_ERR_INTERNAL, std::string(who) + ": bad column counts");
-
+  MatrixPrep prep;
+  const gg_status ps = matrix_prepare(c, who, d_sk, d_lens, n, d_members, P, MatrixForm{MatrixForm::kGroups, 0, d_off, d_seg, G},
+                                      &prep, st);
+  if (ps != GG_OK) return ps;
   if (singles) {
-    hipLaunchKernelGGL(mxg_single_kernel, grid_for(G), dim3(256), 0, st, d_off, d_cell, G, pos_len, d_common, d_total,
+    hipLaunchKernelGGL(mxg_single_kernel, grid_for(G), dim3(256), 0, st, d_off, d_cell, G, prep.pos_len, d_common, d_total,
                        d_ani);
     GG_HIP(c, hipGetLastError());
   }
-  MxGroupLaunch a{};
-  a.sk = d_sk;
-  a.s = s;
-  a.m = 0;
-  a.pos_row = pos_row;
-  a.pos_len = pos_len;
-  a.piece = piece;
-  a.piece_cnt = piece_cnt;
+  MxGroupLaunch a = launch_of<MxGroupLaunch>(c, d_sk, prep);
+  a.m = 0;  // (not read: a workgroup finds its group's positions in offsets)
   a.common = d_common;
   a.total = d_total;
   a.ani = d_ani;
-  a.k = c->k;
   a.offsets = d_off;
   a.tp_off = d_tp;
   a.cell_off = d_cell;
   a.n_groups = G;
-  const dim3 grid(tile_pairs);
-  uint64_t flagged = 0;
-  if (tile_pairs && d_ani) {
-    const gg_status r = ani_flagged_passes(
-        c, who, cells,
-        [&](double E, AniFlagged* list, uint64_t cap, unsigned long long* count) {
-          a.E = E;
-          a.list = list;
-          a.cap = cap;
-          a.count = count;
-          hipLaunchKernelGGL(mx_common_kernel<MxGroupLaunch>, grid, dim3(256), 0, st, a);
-          return hipGetLastError();
-        },
-        d_ani, nullptr, 0, &flagged, st);
-    if (r != GG_OK) return r;
-  } else {
-    if (tile_pairs) {
-      hipLaunchKernelGGL(mx_common_kernel<MxGroupLaunch>, grid, dim3(256), 0, st, a);
-      GG_HIP(c, hipGetLastError());
-    }
-    GG_HIP(c, hipStreamSynchronize(st));
+  // (the tile pairs' and the cells' totals are the host's; both sides of the diagonal are listed: no mirror)
+  return dense_product(c, who, a, h_tp[G], h_cell[G], 0, 1, prep, sum, st);
+}
+
+// ---- the host-input forms: the argument tests and the upload they share ----------
+// The tests come in two steps, since an entry point runs tests of its own
+// before, between and after them; the message goes to `err`.  rows: the row
+// list or the members of `count` positions (null: rows 0 .. count - 1).
+gg_status check_sketch_arrays(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                              const uint32_t* rows, bool rows_needed, uint32_t count, std::string& err) {
+  if ((rows_needed && !rows) || (n && (!sketches || !lens))) {
+    err = w + ": null argument";
+    return GG_ERR_INVALID_ARG;
   }
-  if (sum) {
-    sum->n_entries = n_entries;
-    sum->n_columns = n_columns;
-    sum->column_entries = column_entries;
-    sum->ani_rechecked = flagged;  // cells: both sides of the diagonal are listed
+  if (!rows && count > n) {
+    err = w + ": more positions than rows";
+    return GG_ERR_INVALID_ARG;
+  }
+  return GG_OK;
+}
+
+gg_status check_sketch_rows(const std::string& w, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                            const uint32_t* rows, uint32_t count, bool listed_once, std::string& err) {
+  for (uint32_t g = 0; g < n; ++g)
+    if (lens[g] > sketch_size) {
+      err = w + ": sketch longer than sketch_size";
+      return GG_ERR_INVALID_ARG;
+    }
+  std::vector<uint8_t> seen(rows && listed_once ? n : 0, 0);
+  for (uint32_t a = 0; rows && a < count; ++a) {
+    if (rows[a] >= n) {
+      err = w + ": row index out of range";
+      return GG_ERR_INVALID_ARG;
+    }
+    if (listed_once && seen[rows[a]]++) {
+      err = w + ": row index listed twice";
+      return GG_ERR_INVALID_ARG;
+    }
+  }
+  return GG_OK;
+}
+
+gg_status upload_sketch_rows(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
+                             uint32_t count, uint64_t** d_sk, uint32_t** d_len, uint32_t** d_rows, hipStream_t st) {
+  *d_rows = nullptr;
+  GG_HIP(c, scratch_t(c, "mx_h_sk", (size_t)n * c->s, d_sk));
+  GG_HIP(c, scratch_t(c, "mx_h_len", (size_t)n, d_len));
+  GG_HIP(c, hipMemcpyAsync(*d_sk, sketches, (size_t)n * c->s * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  GG_HIP(c, hipMemcpyAsync(*d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (rows) {
+    GG_HIP(c, scratch_t(c, "mx_h_rows", (size_t)count, d_rows));
+    GG_HIP(c, hipMemcpyAsync(*d_rows, rows, (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
   return GG_OK;
 }
 
 namespace {
 
-// the checks of the host-input forms (the message goes to `err`)
-gg_status check_matrix_input(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
-                             uint32_t sketch_size, int k, const uint32_t* rows, uint32_t m, const void* common,
-                             const void* total, const void* ani, std::string& err) {
+// the checks of the dense host-input forms (the message goes to `err`): rows /
+// count the row list of gg_ani_matrix, or the members of a grouped call, whose
+// offsets (non-null) are checked first; *none: there is no position, nothing is run
+gg_status check_dense_input(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                            uint32_t sketch_size, int k, const uint32_t* rows, uint32_t count, const uint32_t* offsets,
+                            uint32_t n_groups, bool grouped, const void* common, const void* total, const void* ani,
+                            bool* none, std::string& err) {
+  *none = true;
   if (k < 1 || k > 32 || sketch_size < 1) {
     err = w + ": kmer_length must be 1..32 and sketch_size at least 1";
     return GG_ERR_INVALID_ARG;
   }
-  if (m > matrix::kMaxRows) {
+  if (grouped) {
+    const gg_status st = check_group_offsets(w, offsets, n_groups, sketch_size, nullptr, nullptr, err);
+    if (st != GG_OK) return st;
+    count = offsets[n_groups];
+  } else if (count > matrix::kMaxRows) {
     err = w + ": more than 32768 rows listed";
     return GG_ERR_INVALID_ARG;
   }
-  if (m == 0) return GG_OK;
+  if (count == 0) return GG_OK;
+  *none = false;
   if (!common && !total && !ani) {
     err = w + ": no output asked for";
     return GG_ERR_INVALID_ARG;
   }
-  if (n && (!sketches || !lens)) {
-    err = w + ": null argument";
-    return GG_ERR_INVALID_ARG;
-  }
-  if (!rows && m > n) {
-    err = w + ": more positions than rows";
-    return GG_ERR_INVALID_ARG;
-  }
-  for (uint32_t g = 0; g < n; ++g)
-    if (lens[g] > sketch_size) {
-      err = w + ": sketch longer than sketch_size";
-      return GG_ERR_INVALID_ARG;
-    }
-  for (uint32_t a = 0; rows && a < m; ++a)
-    if (rows[a] >= n) {
-      err = w + ": row index out of range";
-      return GG_ERR_INVALID_ARG;
-    }
+  const gg_status st = check_sketch_arrays(w, sketches, lens, n, rows, grouped, count, err);
+  return st != GG_OK ? st : check_sketch_rows(w, lens, n, sketch_size, rows, count, false, err);
+}
+
+// The host frame of the dense forms: the rows up, run(d_sk, d_len, d_rows,
+// d_common, d_total, d_ani) on the context's stream, the outputs asked for down.
+template <class Run>
+gg_status dense_from_host(gg_ctx* pm, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
+                          uint32_t count, size_t cells, uint32_t* common, uint32_t* total, float* ani, const Run& run) {
+  if (hipSetDevice(pm->device) != hipSuccess) return fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  uint64_t* d_sk = nullptr;
+  uint32_t *d_len = nullptr, *d_rows = nullptr, *d_common = nullptr, *d_total = nullptr;
+  float* d_ani = nullptr;
+  gg_status st = upload_sketch_rows(pm, sketches, lens, n, rows, count, &d_sk, &d_len, &d_rows, pm->stream);
+  if (st != GG_OK) return st;
+  if (common) GG_HIP(pm, scratch_t(pm, "mx_h_common", cells, &d_common));
+  if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", cells, &d_total));
+  if (ani) GG_HIP(pm, scratch_t(pm, "mx_h_ani", cells, &d_ani));
+  st = run(d_sk, d_len, d_rows, d_common, d_total, d_ani);
+  if (st != GG_OK) return st;
+  if (common) GG_HIP(pm, hipMemcpyAsync(common, d_common, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  if (total) GG_HIP(pm, hipMemcpyAsync(total, d_total, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  if (ani) GG_HIP(pm, hipMemcpyAsync(ani, d_ani, cells * 4, hipMemcpyDeviceToHost, pm->stream));
+  GG_HIP(pm, hipStreamSynchronize(pm->stream));
   return GG_OK;
 }
 
 gg_status ani_matrix_ctx(gg_ctx* pm, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
                          uint32_t m, uint32_t* common, uint32_t* total, float* ani, gg_matrix_summary* summary) {
   std::string err;
-  const gg_status chk = check_matrix_input("gg_ani_matrix", sketches, lens, n, pm->s, pm->k, rows, m, common, total, ani,
-                                           err);
+  bool none;
+  const gg_status chk = check_dense_input("gg_ani_matrix", sketches, lens, n, pm->s, pm->k, rows, m, nullptr, 0, false,
+                                          common, total, ani, &none, err);
   if (chk != GG_OK) return fail(pm, chk, err);
-  if (m == 0) return GG_OK;
-  if (hipSetDevice(pm->device) != hipSuccess) return fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  const size_t cells = (size_t)m * m;
-  uint64_t* d_sk = nullptr;
-  uint32_t *d_len = nullptr, *d_rows = nullptr, *d_common = nullptr, *d_total = nullptr;
-  float* d_ani = nullptr;
-  GG_HIP(pm, scratch_t(pm, "mx_h_sk", (size_t)n * pm->s, &d_sk));
-  GG_HIP(pm, scratch_t(pm, "mx_h_len", (size_t)n, &d_len));
-  GG_HIP(pm, hipMemcpyAsync(d_sk, sketches, (size_t)n * pm->s * sizeof(uint64_t), hipMemcpyHostToDevice, pm->stream));
-  GG_HIP(pm, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
-  if (rows) {
-    GG_HIP(pm, scratch_t(pm, "mx_h_rows", (size_t)m, &d_rows));
-    GG_HIP(pm, hipMemcpyAsync(d_rows, rows, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
-  }
-  if (common) GG_HIP(pm, scratch_t(pm, "mx_h_common", cells, &d_common));
-  if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", cells, &d_total));
-  if (ani) GG_HIP(pm, scratch_t(pm, "mx_h_ani", cells, &d_ani));
-  const gg_status st = ani_matrix_device(pm, d_sk, d_len, n, d_rows, m, d_common, d_total, d_ani, summary, pm->stream);
-  if (st != GG_OK) return st;
-  if (common) GG_HIP(pm, hipMemcpyAsync(common, d_common, cells * 4, hipMemcpyDeviceToHost, pm->stream));
-  if (total) GG_HIP(pm, hipMemcpyAsync(total, d_total, cells * 4, hipMemcpyDeviceToHost, pm->stream));
-  if (ani) GG_HIP(pm, hipMemcpyAsync(ani, d_ani, cells * 4, hipMemcpyDeviceToHost, pm->stream));
-  GG_HIP(pm, hipStreamSynchronize(pm->stream));
-  return GG_OK;
-}
-
-// the checks of the grouped host-input forms: check_matrix_input's, applied to members and offsets
-gg_status check_groups_input(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
-                             uint32_t sketch_size, int k, const uint32_t* members, const uint32_t* offsets,
-                             uint32_t n_groups, const void* common, const void* total, const void* ani,
-                             std::string& err) {
-  if (k < 1 || k > 32 || sketch_size < 1) {
-    err = w + ": kmer_length must be 1..32 and sketch_size at least 1";
-    return GG_ERR_INVALID_ARG;
-  }
-  const gg_status st = check_group_offsets(w, offsets, n_groups, sketch_size, nullptr, nullptr, err);
-  if (st != GG_OK) return st;
-  const uint32_t P = offsets[n_groups];
-  if (P == 0) return GG_OK;
-  if (!common && !total && !ani) {
-    err = w + ": no output asked for";
-    return GG_ERR_INVALID_ARG;
-  }
-  if (!members || (n && (!sketches || !lens))) {
-    err = w + ": null argument";
-    return GG_ERR_INVALID_ARG;
-  }
-  for (uint32_t g = 0; g < n; ++g)
-    if (lens[g] > sketch_size) {
-      err = w + ": sketch longer than sketch_size";
-      return GG_ERR_INVALID_ARG;
-    }
-  for (uint32_t p = 0; p < P; ++p)
-    if (members[p] >= n) {
-      err = w + ": row index out of range";
-      return GG_ERR_INVALID_ARG;
-    }
-  return GG_OK;
+  if (none) return GG_OK;
+  return dense_from_host(pm, sketches, lens, n, rows, m, (size_t)m * m, common, total, ani,
+                         [&](const uint64_t* d_sk, const uint32_t* d_len, const uint32_t* d_rows, uint32_t* d_common,
+                             uint32_t* d_total, float* d_ani) {
+                           return ani_matrix_device(pm, d_sk, d_len, n, d_rows, m, d_common, d_total, d_ani, summary,
+                                                    pm->stream);
+                         });
 }
 
 gg_status ani_matrix_groups_ctx(gg_ctx* pm, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
                                 const uint32_t* members, const uint32_t* offsets, uint32_t n_groups, uint32_t* common,
                                 uint32_t* total, float* ani, gg_matrix_summary* summary) {
   std::string err;
-  const gg_status chk = check_groups_input("gg_ani_matrix_groups", sketches, lens, n, pm->s, pm->k, members, offsets,
-                                           n_groups, common, total, ani, err);
+  bool none;
+  const gg_status chk = check_dense_input("gg_ani_matrix_groups", sketches, lens, n, pm->s, pm->k, members, 0, offsets,
+                                          n_groups, true, common, total, ani, &none, err);
   if (chk != GG_OK) return fail(pm, chk, err);
-  const uint32_t P = offsets[n_groups];
-  if (P == 0) return GG_OK;
-  if (hipSetDevice(pm->device) != hipSuccess) return fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  if (none) return GG_OK;
   uint64_t cells = 0;
   for (uint32_t g = 0; g < n_groups; ++g) cells += (uint64_t)(offsets[g + 1] - offsets[g]) * (offsets[g + 1] - offsets[g]);
-  uint64_t* d_sk = nullptr;
-  uint32_t *d_len = nullptr, *d_members = nullptr, *d_common = nullptr, *d_total = nullptr;
-  float* d_ani = nullptr;
-  GG_HIP(pm, scratch_t(pm, "mx_h_sk", (size_t)n * pm->s, &d_sk));
-  GG_HIP(pm, scratch_t(pm, "mx_h_len", (size_t)n, &d_len));
-  GG_HIP(pm, scratch_t(pm, "mx_h_rows", (size_t)P, &d_members));
-  GG_HIP(pm, hipMemcpyAsync(d_sk, sketches, (size_t)n * pm->s * sizeof(uint64_t), hipMemcpyHostToDevice, pm->stream));
-  GG_HIP(pm, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
-  GG_HIP(pm, hipMemcpyAsync(d_members, members, (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, pm->stream));
-  if (common) GG_HIP(pm, scratch_t(pm, "mx_h_common", (size_t)cells, &d_common));
-  if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", (size_t)cells, &d_total));
-  if (ani) GG_HIP(pm, scratch_t(pm, "mx_h_ani", (size_t)cells, &d_ani));
-  const gg_status st = ani_matrix_groups_device(pm, d_sk, d_len, n, d_members, offsets, n_groups, d_common, d_total,
-                                                d_ani, summary, pm->stream);
-  if (st != GG_OK) return st;
-  if (common) GG_HIP(pm, hipMemcpyAsync(common, d_common, cells * 4, hipMemcpyDeviceToHost, pm->stream));
-  if (total) GG_HIP(pm, hipMemcpyAsync(total, d_total, cells * 4, hipMemcpyDeviceToHost, pm->stream));
-  if (ani) GG_HIP(pm, hipMemcpyAsync(ani, d_ani, cells * 4, hipMemcpyDeviceToHost, pm->stream));
-  GG_HIP(pm, hipStreamSynchronize(pm->stream));
-  return GG_OK;
+  return dense_from_host(pm, sketches, lens, n, members, offsets[n_groups], (size_t)cells, common, total, ani,
+                         [&](const uint64_t* d_sk, const uint32_t* d_len, const uint32_t* d_members, uint32_t* d_common,
+                             uint32_t* d_total, float* d_ani) {
+                           return ani_matrix_groups_device(pm, d_sk, d_len, n, d_members, offsets, n_groups, d_common,
+                                                           d_total, d_ani, summary, pm->stream);
+                         });
 }
 
 }  // namespace
@@ -1201,8 +1144,9 @@ gg_status gg_ani_matrix_host(const uint64_t* sketches, const uint32_t* lens, uin
                              int kmer_length, const uint32_t* rows, uint32_t m, uint32_t* common, uint32_t* total,
                              float* ani) {
   std::string err;
-  const gg_status st = check_matrix_input("gg_ani_matrix_host", sketches, lens, n, sketch_size, kmer_length, rows, m,
-                                          common, total, ani, err);
+  bool none;
+  const gg_status st = check_dense_input("gg_ani_matrix_host", sketches, lens, n, sketch_size, kmer_length, rows, m,
+                                         nullptr, 0, false, common, total, ani, &none, err);
   if (st != GG_OK) {
     set_thread_error(err);
     return st;
@@ -1230,11 +1174,7 @@ gg_status gg_ani_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* l
   gg_ctx* pm = primary(ctx);
   if (summary) *summary = gg_matrix_summary{};
   const gg_status st = ani_matrix_ctx(pm, sketches, lens, n, rows, m, common, total, ani, summary);
-  if (st != GG_OK) {
-    if (summary) *summary = gg_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_matrix_summary{}; });
 }
 
 gg_status gg_ani_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
@@ -1254,11 +1194,7 @@ gg_status gg_ani_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const ui
     st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
   else
     st = ani_matrix_device(pm, d_sketches, d_lens, n, d_rows, m, d_common, d_total, d_ani, summary, (hipStream_t)stream);
-  if (st != GG_OK) {
-    if (summary) *summary = gg_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_matrix_summary{}; });
 }
 
 gg_status gg_ani_matrix_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, const char* cache_dir,
@@ -1294,8 +1230,9 @@ gg_status gg_ani_matrix_groups_host(const uint64_t* sketches, const uint32_t* le
                                     int kmer_length, const uint32_t* members, const uint32_t* offsets,
                                     uint32_t n_groups, uint32_t* common, uint32_t* total, float* ani) {
   std::string err;
-  const gg_status st = check_groups_input("gg_ani_matrix_groups_host", sketches, lens, n, sketch_size, kmer_length,
-                                          members, offsets, n_groups, common, total, ani, err);
+  bool none;
+  const gg_status st = check_dense_input("gg_ani_matrix_groups_host", sketches, lens, n, sketch_size, kmer_length,
+                                         members, 0, offsets, n_groups, true, common, total, ani, &none, err);
   if (st != GG_OK) {
     set_thread_error(err);
     return st;
@@ -1328,11 +1265,7 @@ gg_status gg_ani_matrix_groups(gg_ctx* ctx, const uint64_t* sketches, const uint
   if (summary) *summary = gg_matrix_summary{};
   const gg_status st = ani_matrix_groups_ctx(pm, sketches, lens, n, members, offsets, n_groups, common, total, ani,
                                              summary);
-  if (st != GG_OK) {
-    if (summary) *summary = gg_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_matrix_summary{}; });
 }
 
 gg_status gg_ani_matrix_groups_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
@@ -1355,11 +1288,7 @@ gg_status gg_ani_matrix_groups_device(gg_ctx* ctx, const uint64_t* d_sketches, c
   else
     st = ani_matrix_groups_device(pm, d_sketches, d_lens, n, d_members, offsets, n_groups, d_common, d_total, d_ani,
                                   summary, (hipStream_t)stream);
-  if (st != GG_OK) {
-    if (summary) *summary = gg_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_matrix_summary{}; });
 }
 
 }  // extern "C"

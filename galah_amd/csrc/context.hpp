@@ -290,12 +290,24 @@ gg_status ani_matrix_groups_device(gg_ctx* c, const uint64_t* d_sk, const uint32
                                    const uint32_t* d_members, const uint32_t* offsets, uint32_t n_groups,
                                    uint32_t* d_common, uint32_t* d_total, float* d_ani, gg_matrix_summary* sum,
                                    hipStream_t st);
-// The positions part of a matrix call (ani_matrix.hip), in context scratch
-// until the next matrix call on the context, and the counts read back.
-// border_n_old != kNoBorder (then m == n >= border_n_old, d_rows is not read):
-// the border form (matrix_core.hpp) -- the new rows at the first positions,
-// the border column rule, and new_entries, the kept entries of the new rows.
-constexpr uint32_t kNoBorder = 0xFFFFFFFFu;
+// The positions part of a matrix call (ani_matrix.hip), the one of every form,
+// in context scratch until the next matrix call on the context, and the counts
+// read back.  The form (matrix_core.hpp):
+//   kRows    the m rows listed in d_rows (null: rows 0 .. m-1);
+//   kBorder  m == n >= n_old, d_rows is not read: the new rows at the first
+//            positions, the border column rule, and new_entries, the kept
+//            entries of the new rows;
+//   kGroups  d_rows the members of n_groups groups, group g at positions
+//            d_offsets[g] .. d_offsets[g+1] (device words): columns and ids per
+//            group; d_seg [n_groups + 1] device words, which receive every
+//            group's first sorted entry.
+struct MatrixForm {
+  enum Kind { kRows, kBorder, kGroups } kind = kRows;
+  uint32_t n_old = 0;
+  const uint32_t* d_offsets = nullptr;
+  uint32_t* d_seg = nullptr;
+  uint32_t n_groups = 0;
+};
 struct MatrixPrep {
   const uint32_t *pos_row, *pos_len, *piece, *piece_cnt;
   uint32_t m;
@@ -303,16 +315,37 @@ struct MatrixPrep {
   uint64_t new_entries = 0;
 };
 gg_status matrix_prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                         const uint32_t* d_rows, uint32_t m, MatrixPrep* out, hipStream_t st,
-                         uint32_t border_n_old = kNoBorder);
+                         const uint32_t* d_rows, uint32_t m, const MatrixForm& form, MatrixPrep* out, hipStream_t st);
+// What the host-input forms of the matrix calls share (ani_matrix.hip): the
+// argument tests in two steps, the message to `err` -- null arrays (rows too
+// when rows_needed) and more positions than rows; then a sketch longer than
+// sketch_size, a row index out of range and, with listed_once, one listed
+// twice -- and the upload of the rows (and of `count` row indices, rows
+// non-null) into context scratch, enqueued on st.
+gg_status check_sketch_arrays(const std::string& w, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                              const uint32_t* rows, bool rows_needed, uint32_t count, std::string& err);
+gg_status check_sketch_rows(const std::string& w, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
+                            const uint32_t* rows, uint32_t count, bool listed_once, std::string& err);
+gg_status upload_sketch_rows(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
+                             uint32_t count, uint64_t** d_sk, uint32_t** d_len, uint32_t** d_rows, hipStream_t st);
+// The tail of an extern "C" entry point that ran on pm = primary(ctx): on
+// failure on_failure() puts the outputs back and the message goes to ctx.
+template <typename OnFailure>
+gg_status finish_call(gg_ctx* ctx, gg_ctx* pm, gg_status st, const OnFailure& on_failure) {
+  if (st != GG_OK) {
+    on_failure();
+    if (pm != ctx) ctx->err = pm->err;
+  }
+  return st;
+}
 // The pair form of the product (ani_matrix.hip, matrix_core.hpp): the passing
 // pairs of the prepared positions appended to d_out, gg_pairs_device's output
 // contract.  d_cmin / d_sufmin: pairs_tables'.  Asynchronous.
 gg_status pairs_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, const uint32_t* d_cmin,
                               const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
                               hipStream_t st);
-// The border form of it over positions prepared with
-// border_n_old = p.m - n_new.  Asynchronous.
+// The border form of it over positions prepared as a border
+// of n_old = p.m - n_new.  Asynchronous.
 gg_status pairs_border_matrix_launch(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, uint32_t n_new,
                                      const uint32_t* d_cmin, const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap,
                                      uint64_t* d_count, hipStream_t st);

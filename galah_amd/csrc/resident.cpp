@@ -30,7 +30,7 @@ namespace {
 // index's member reads exceed R chunk rounds (changes no result)
 constexpr double kPairsMatrixRatio = 3675.0;  // (measured)
 constexpr double kBorderMatrixRatio = 1000.0;  // a border call's (measured)
-double pairs_matrix_ratio(double dflt = kPairsMatrixRatio) {
+double pairs_matrix_ratio(double dflt) {
   const char* e = getenv("GALAHGPU_PAIRS_MATRIX_RATIO");
   if (!e || !*e) return dflt;
   char* end = nullptr;
@@ -45,13 +45,49 @@ uint64_t test_pairs_cap(uint64_t cap) {
   return std::min<uint64_t>(cap, std::max<uint64_t>(1, strtoull(e, nullptr, 10)));
 }
 
-void fill_matrix_summary(gg_pairs_matrix_summary* sum, const MatrixPrep& p) {
-  sum->n_entries = p.n_entries;
-  sum->n_columns = p.n_columns;
-  sum->column_entries = p.column_entries;
-  sum->chunk_rounds = matrix::pair_chunk_rounds(p.m, p.n_columns);
-  sum->index_reads = matrix::pair_index_reads(p.n_columns, p.column_entries);
-}
+// What differs between the two forms of the product that give pairs: the pair
+// form over m positions, and the border form (4.13) over all
+// m == n rows of which the first n_old are old.
+struct PairsForm {
+  uint32_t m;
+  bool border;
+  uint32_t n_old;
+  bool work() const { return m >= 2 && !(border && n_old == m); }  // there is a pair to evaluate
+  bool limits_ok(uint32_t s) const { return border ? matrix::border_limits_ok(m, n_old, s) : matrix::pair_limits_ok(m, s); }
+  uint64_t all() const {
+    const uint64_t n_new = border ? m - n_old : m, old = m - n_new;
+    return n_new * old + n_new * (n_new - 1) / 2;
+  }
+  double ratio() const { return border ? kBorderMatrixRatio : kPairsMatrixRatio; }
+  gg_status prepare(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                    const uint32_t* d_rows, MatrixPrep* prep, hipStream_t st) const {
+    return matrix_prepare(c, who, d_sk, d_lens, n, d_rows, m, border ? MatrixForm{MatrixForm::kBorder, n_old} : MatrixForm{},
+                          prep, st);
+  }
+  // the tables of min_ani and the launch: asynchronous
+  gg_status run(gg_ctx* c, const uint64_t* d_sk, const MatrixPrep& p, float min_ani, gg_pair* d_out, uint64_t cap,
+                uint64_t* d_count, hipStream_t st) const {
+    uint32_t *d_cmin, *d_sufmin;
+    const gg_status t = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
+    if (t != GG_OK) return t;
+    return border ? pairs_border_matrix_launch(c, d_sk, p, m - n_old, d_cmin, d_sufmin, d_out, cap, d_count, st)
+                  : pairs_matrix_launch(c, d_sk, p, d_cmin, d_sufmin, d_out, cap, d_count, st);
+  }
+  void fill(gg_pairs_matrix_summary* sum, const MatrixPrep& p) const {
+    sum->n_entries = p.n_entries;
+    sum->n_columns = p.n_columns;
+    sum->column_entries = p.column_entries;
+    sum->chunk_rounds = border ? matrix::border_chunk_rounds(p.m, n_old, p.n_columns) : matrix::pair_chunk_rounds(p.m, p.n_columns);
+    sum->index_reads = border ? matrix::border_index_reads(p.n_columns, p.column_entries, p.new_entries)
+                              : matrix::pair_index_reads(p.n_columns, p.column_entries);
+  }
+  void fill(gg_pairs_matrix_summary* sum, const MatrixPrep& p, uint64_t n_pairs, uint32_t passes) const {
+    fill(sum, p);
+    sum->n_pairs = n_pairs;
+    sum->path = GG_PAIRS_PATH_MATRIX;
+    sum->pair_passes = passes;
+  }
+};
 
 // The sized passes of a pair producer into scratch `key`: the first at `cap`,
 // one retry at the exact count.  run(d_out, cap, d_count) enqueues it on st.
@@ -85,68 +121,52 @@ gg_status sized_pair_passes(gg_ctx* c, const std::string& who, const char* key, 
   return GG_OK;
 }
 
-}  // namespace
-
-gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                            float min_ani, gg_pair** d_pairs, uint64_t* n_pairs, uint32_t* n_passes, hipStream_t st,
-                            gg_pairs_matrix_summary* msum) {
-  *d_pairs = nullptr;
-  *n_pairs = 0;
-  *n_passes = 0;
-  if (msum) *msum = gg_pairs_matrix_summary{};
-  if (n < 2) return GG_OK;
-  const uint64_t all = (uint64_t)n * (n - 1) / 2;
-  const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all);
-  // the matrix: by request, or by AUTO's rule from the counts of the positions part
-  bool matrix = false;
-  MatrixPrep prep{};
-  gg_pairs_matrix_summary ms{};
-  if (c->pairs_path != GG_PAIRS_PATH_DEFAULT) {
-    const bool fits = matrix::pair_limits_ok(n, c->s);
-    if (c->pairs_path == GG_PAIRS_PATH_MATRIX && !fits)
-      return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more, on the matrix path");
-    if (fits) {
-      const gg_status r = matrix_prepare(c, who, d_sk, d_lens, n, nullptr, n, &prep, st);
-      if (r != GG_OK) return r;
-      fill_matrix_summary(&ms, prep);
-      matrix = c->pairs_path == GG_PAIRS_PATH_MATRIX ||
-               (prep.n_columns > 0 && (double)ms.index_reads > pairs_matrix_ratio() * (double)ms.chunk_rounds);
-    }
-  }
-  gg_status r;
-  if (matrix) {
-    uint32_t *d_cmin, *d_sufmin;
-    r = sized_pair_passes(
-        c, who, "rs_pairs", all, cap,
-        [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) {
-          const gg_status t = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
-          return t != GG_OK ? t : pairs_matrix_launch(c, d_sk, prep, d_cmin, d_sufmin, d_out, pcap, d_count, st);
-        },
-        d_pairs, n_pairs, n_passes, st);
-  } else {
-    r = sized_pair_passes(
-        c, who, "rs_pairs", all, cap,
-        [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) {
-          return pairs_core(c, d_sk, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, pcap, d_count, st);
-        },
-        d_pairs, n_pairs, n_passes, st);
-  }
+// The route of a call over resident rows by the context's pairs path.
+// DEFAULT: nothing is run.  MATRIX: the positions part, or GG_ERR_INVALID_ARG
+// when the limits fail.  AUTO: the positions part when the limits hold, and
+// the product iff there is a column and index_reads > R * chunk_rounds (R:
+// GALAHGPU_PAIRS_MATRIX_RATIO, by default the form's own: 3,675, or a
+// border's 1,000).  *ms: the counts whenever the positions part ran.
+gg_status matrix_route(gg_ctx* c, const char* who, const PairsForm& form, const uint64_t* d_sk, const uint32_t* d_lens,
+                       uint32_t n, hipStream_t st, bool* matrix, MatrixPrep* prep, gg_pairs_matrix_summary* ms) {
+  *matrix = false;
+  if (c->pairs_path == GG_PAIRS_PATH_DEFAULT) return GG_OK;
+  const bool fits = form.limits_ok(c->s);
+  if (c->pairs_path == GG_PAIRS_PATH_MATRIX && !fits)
+    return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more, on the matrix path");
+  if (!fits) return GG_OK;
+  const gg_status r = form.prepare(c, who, d_sk, d_lens, n, nullptr, prep, st);
   if (r != GG_OK) return r;
-  ++c->pairs_paths_taken[!matrix ? 0 : c->pairs_path == GG_PAIRS_PATH_MATRIX ? 1 : 2];
-  if (msum) {
-    *msum = ms;
-    msum->n_pairs = *n_pairs;
-    msum->path = matrix ? GG_PAIRS_PATH_MATRIX : GG_PAIRS_PATH_DEFAULT;
-    msum->pair_passes = *n_passes;
-  }
+  form.fill(ms, *prep);
+  *matrix = c->pairs_path == GG_PAIRS_PATH_MATRIX ||
+            (prep->n_columns > 0 && (double)ms->index_reads > pairs_matrix_ratio(form.ratio()) * (double)ms->chunk_rounds);
   return GG_OK;
 }
 
-// gg_pairs_matrix_device behind its argument checks
-gg_status pairs_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint32_t* d_rows,
-                              uint32_t m, float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
-                              gg_pairs_matrix_summary* sum, hipStream_t st) {
-  if (m < 2) {  // no pair: nothing is run
+// The middle of the host frame: the pairs of prepared positions into context
+// scratch, sorted by (i, j) -- the first capacity min(all pairs of the form,
+// max(2^20, 16 m)), one retry at the exact count.
+gg_status pairs_form_sorted(gg_ctx* c, const char* who, const PairsForm& form, const uint64_t* d_sk, const MatrixPrep& prep,
+                            uint32_t n, float min_ani, gg_pair** d_sorted, uint64_t* cnt, uint32_t* passes,
+                            hipStream_t st) {
+  const uint64_t all = form.all();
+  const uint64_t cap = test_pairs_cap(std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)form.m * 16), all));
+  gg_pair* d_pairs = nullptr;
+  const gg_status r = sized_pair_passes(
+      c, who, "pm_pairs", all, cap,
+      [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) { return form.run(c, d_sk, prep, min_ani, d_out, pcap, d_count, st); },
+      &d_pairs, cnt, passes, st);
+  if (r != GG_OK) return r;
+  return sorted_pairs_device(c, d_pairs, *cnt, n, d_sorted, st);
+}
+
+// The device frame (gg_pairs_matrix_device, gg_pairs_border_matrix_device
+// behind their argument checks): the count before, the positions part, the
+// tables, the launch, the count after, the summary.
+gg_status pairs_form_device(gg_ctx* c, const char* who, const PairsForm& form, const uint64_t* d_sk, const uint32_t* d_lens,
+                            uint32_t n, const uint32_t* d_rows, float min_ani, gg_pair* d_out, uint64_t cap,
+                            uint64_t* d_count, gg_pairs_matrix_summary* sum, hipStream_t st) {
+  if (!form.work()) {  // no pair: nothing is run, the count is left as it is
     if (sum) sum->path = GG_PAIRS_PATH_MATRIX;
     return GG_OK;
   }
@@ -156,47 +176,24 @@ gg_status pairs_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d
     GG_HIP(c, hipMemcpyAsync(&h_count[0], d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   }
   MatrixPrep prep;
-  gg_status r = matrix_prepare(c, "gg_pairs_matrix", d_sk, d_lens, n, d_rows, m, &prep, st);
+  gg_status r = form.prepare(c, who, d_sk, d_lens, n, d_rows, &prep, st);
   if (r != GG_OK) return r;
-  uint32_t *d_cmin, *d_sufmin;
-  r = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
-  if (r != GG_OK) return r;
-  r = pairs_matrix_launch(c, d_sk, prep, d_cmin, d_sufmin, d_out, cap, d_count, st);
+  r = form.run(c, d_sk, prep, min_ani, d_out, cap, d_count, st);
   if (r != GG_OK) return r;
   if (sum) {
     GG_HIP(c, hipMemcpyAsync(&h_count[1], d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     GG_HIP(c, hipStreamSynchronize(st));
-    fill_matrix_summary(sum, prep);
-    sum->n_pairs = h_count[1] - h_count[0];
-    sum->path = GG_PAIRS_PATH_MATRIX;
-    sum->pair_passes = 1;
+    form.fill(sum, prep, h_count[1] - h_count[0], 1);
   }
   return GG_OK;
 }
 
-// gg_pairs_matrix behind its context lookup: host arrays in, the sorted list out
-gg_status pairs_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
-                           uint32_t m, float min_ani, gg_pair** out, uint64_t* n_out, gg_pairs_matrix_summary* sum) {
-  const char* who = "gg_pairs_matrix";
-  if (!out || !n_out) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  *out = nullptr;
-  *n_out = 0;
-  if (std::isnan(min_ani)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": min_ani is NaN");
-  if (n && (!sketches || !lens)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  if (!rows && m > n) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": more positions than rows");
-  if (!matrix::pair_limits_ok(m, c->s) || !matrix::pair_limits_ok(n, c->s))
-    return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more");
-  for (uint32_t g = 0; g < n; ++g)
-    if (lens[g] > c->s) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": sketch longer than sketch_size");
-  if (rows) {
-    std::vector<uint8_t> seen(n, 0);
-    for (uint32_t a = 0; a < m; ++a) {
-      if (rows[a] >= n) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": row index out of range");
-      if (seen[rows[a]]) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": row index listed twice");
-      seen[rows[a]] = 1;
-    }
-  }
-  if (m < 2) {  // no pair: nothing is run
+// The host frame (gg_pairs_matrix, gg_pairs_border_matrix behind their
+// argument checks): host arrays in, the sorted list out.
+gg_status pairs_form_host(gg_ctx* c, const char* who, const PairsForm& form, const uint64_t* sketches, const uint32_t* lens,
+                          uint32_t n, const uint32_t* rows, float min_ani, gg_pair** out, uint64_t* n_out,
+                          gg_pairs_matrix_summary* sum) {
+  if (!form.work()) {  // no pair: nothing is run
     if (sum) sum->path = GG_PAIRS_PATH_MATRIX;
     *out = (gg_pair*)malloc(sizeof(gg_pair));
     return *out ? GG_OK : fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
@@ -205,183 +202,59 @@ gg_status pairs_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* 
   hipStream_t st = c->stream;
   uint64_t* d_sk = nullptr;
   uint32_t *d_len = nullptr, *d_rows = nullptr;
-  GG_HIP(c, scratch_t(c, "mx_h_sk", (size_t)n * c->s, &d_sk));
-  GG_HIP(c, scratch_t(c, "mx_h_len", (size_t)n, &d_len));
-  GG_HIP(c, hipMemcpyAsync(d_sk, sketches, (size_t)n * c->s * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  GG_HIP(c, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (rows) {
-    GG_HIP(c, scratch_t(c, "mx_h_rows", (size_t)m, &d_rows));
-    GG_HIP(c, hipMemcpyAsync(d_rows, rows, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  }
+  gg_status r = upload_sketch_rows(c, sketches, lens, n, rows, form.m, &d_sk, &d_len, &d_rows, st);
+  if (r != GG_OK) return r;
   MatrixPrep prep;
-  gg_status r = matrix_prepare(c, who, d_sk, d_len, n, d_rows, m, &prep, st);
-  if (r != GG_OK) return r;
-  const uint64_t all = (uint64_t)m * (m - 1) / 2;
-  const uint64_t cap = test_pairs_cap(std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)m * 16), all));
-  gg_pair *d_pairs = nullptr, *d_sorted = nullptr;
-  uint64_t cnt = 0;
-  uint32_t passes = 0, *d_cmin, *d_sufmin;
-  r = sized_pair_passes(
-      c, who, "pm_pairs", all, cap,
-      [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) {
-        const gg_status t = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
-        return t != GG_OK ? t : pairs_matrix_launch(c, d_sk, prep, d_cmin, d_sufmin, d_out, pcap, d_count, st);
-      },
-      &d_pairs, &cnt, &passes, st);
-  if (r != GG_OK) return r;
-  r = sorted_pairs_device(c, d_pairs, cnt, n, &d_sorted, st);
-  if (r != GG_OK) return r;
-  *out = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
-  if (!*out) return fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-  if (cnt) GG_HIP(c, hipMemcpyAsync(*out, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
-  GG_HIP(c, hipStreamSynchronize(st));
-  *n_out = cnt;
-  if (sum) {
-    fill_matrix_summary(sum, prep);
-    sum->n_pairs = cnt;
-    sum->path = GG_PAIRS_PATH_MATRIX;
-    sum->pair_passes = passes;
-  }
-  return GG_OK;
-}
-
-// ---- the border form ------------------------------------------
-namespace {
-
-uint64_t border_all_pairs(uint32_t n, uint32_t n_old) {
-  const uint64_t n_new = n - n_old;
-  return n_new * n_old + n_new * (n_new - 1) / 2;
-}
-
-void fill_border_summary(gg_pairs_matrix_summary* sum, const MatrixPrep& p, uint32_t n_old) {
-  sum->n_entries = p.n_entries;
-  sum->n_columns = p.n_columns;
-  sum->column_entries = p.column_entries;
-  sum->chunk_rounds = matrix::border_chunk_rounds(p.m, n_old, p.n_columns);
-  sum->index_reads = matrix::border_index_reads(p.n_columns, p.column_entries, p.new_entries);
-}
-
-// gg_pairs_border_matrix_device behind its argument checks (n >= 2, n_old < n)
-gg_status pairs_border_matrix_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, uint32_t n_old,
-                                     float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count,
-                                     gg_pairs_matrix_summary* sum, hipStream_t st) {
-  const char* who = "gg_pairs_border_matrix";
-  uint64_t* h_count = nullptr;
-  if (sum) {  // the count before, read with the positions part's read-back
-    GG_HIP(c, host_scratch_t(c, "pm_count", 2, &h_count));
-    GG_HIP(c, hipMemcpyAsync(&h_count[0], d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  }
-  MatrixPrep prep;
-  gg_status r = matrix_prepare(c, who, d_sk, d_lens, n, nullptr, n, &prep, st, n_old);
-  if (r != GG_OK) return r;
-  uint32_t *d_cmin, *d_sufmin;
-  r = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
-  if (r != GG_OK) return r;
-  r = pairs_border_matrix_launch(c, d_sk, prep, n - n_old, d_cmin, d_sufmin, d_out, cap, d_count, st);
-  if (r != GG_OK) return r;
-  if (sum) {
-    GG_HIP(c, hipMemcpyAsync(&h_count[1], d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    GG_HIP(c, hipStreamSynchronize(st));
-    fill_border_summary(sum, prep, n_old);
-    sum->n_pairs = h_count[1] - h_count[0];
-    sum->path = GG_PAIRS_PATH_MATRIX;
-    sum->pair_passes = 1;
-  }
-  return GG_OK;
-}
-
-// The border of prepared positions into context scratch, sorted by (i, j):
-// the first capacity min(all border pairs, max(2^20, 16 n)), one retry at the
-// exact count.
-gg_status border_matrix_sorted(gg_ctx* c, const char* who, const uint64_t* d_sk, const MatrixPrep& prep, uint32_t n,
-                               uint32_t n_old, float min_ani, gg_pair** d_sorted, uint64_t* cnt, uint32_t* passes,
-                               hipStream_t st) {
-  const uint64_t all = border_all_pairs(n, n_old);
-  const uint64_t cap = test_pairs_cap(std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all));
-  gg_pair* d_pairs = nullptr;
-  uint32_t *d_cmin, *d_sufmin;
-  const gg_status r = sized_pair_passes(
-      c, who, "pm_pairs", all, cap,
-      [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) {
-        const gg_status t = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
-        return t != GG_OK ? t
-                          : pairs_border_matrix_launch(c, d_sk, prep, n - n_old, d_cmin, d_sufmin, d_out, pcap, d_count, st);
-      },
-      &d_pairs, cnt, passes, st);
-  if (r != GG_OK) return r;
-  return sorted_pairs_device(c, d_pairs, *cnt, n, d_sorted, st);
-}
-
-// gg_pairs_border_matrix behind its context lookup: host arrays in, the sorted list out
-gg_status pairs_border_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
-                                  float min_ani, gg_pair** out, uint64_t* n_out, gg_pairs_matrix_summary* sum) {
-  const char* who = "gg_pairs_border_matrix";
-  if (!out || !n_out) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  *out = nullptr;
-  *n_out = 0;
-  if (std::isnan(min_ani)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": min_ani is NaN");
-  if (n_old > n) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": n_old exceeds n");
-  if (!matrix::border_limits_ok(n, n_old, c->s))
-    return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more");
-  if (n && (!sketches || !lens)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
-  for (uint32_t g = 0; g < n; ++g)
-    if (lens[g] > c->s) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": sketch longer than sketch_size");
-  if (n < 2 || n_old == n) {  // no pair: nothing is run
-    if (sum) sum->path = GG_PAIRS_PATH_MATRIX;
-    *out = (gg_pair*)malloc(sizeof(gg_pair));
-    return *out ? GG_OK : fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-  }
-  if (hipSetDevice(c->device) != hipSuccess) return fail(c, GG_ERR_HIP, "hipSetDevice failed");
-  hipStream_t st = c->stream;
-  uint64_t* d_sk = nullptr;
-  uint32_t* d_len = nullptr;
-  GG_HIP(c, scratch_t(c, "mx_h_sk", (size_t)n * c->s, &d_sk));
-  GG_HIP(c, scratch_t(c, "mx_h_len", (size_t)n, &d_len));
-  GG_HIP(c, hipMemcpyAsync(d_sk, sketches, (size_t)n * c->s * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  GG_HIP(c, hipMemcpyAsync(d_len, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  MatrixPrep prep;
-  gg_status r = matrix_prepare(c, who, d_sk, d_len, n, nullptr, n, &prep, st, n_old);
+  r = form.prepare(c, who, d_sk, d_len, n, d_rows, &prep, st);
   if (r != GG_OK) return r;
   gg_pair* d_sorted = nullptr;
   uint64_t cnt = 0;
   uint32_t passes = 0;
-  r = border_matrix_sorted(c, who, d_sk, prep, n, n_old, min_ani, &d_sorted, &cnt, &passes, st);
+  r = pairs_form_sorted(c, who, form, d_sk, prep, n, min_ani, &d_sorted, &cnt, &passes, st);
   if (r != GG_OK) return r;
   *out = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
   if (!*out) return fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
   if (cnt) GG_HIP(c, hipMemcpyAsync(*out, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
   GG_HIP(c, hipStreamSynchronize(st));
   *n_out = cnt;
-  if (sum) {
-    fill_border_summary(sum, prep, n_old);
-    sum->n_pairs = cnt;
-    sum->path = GG_PAIRS_PATH_MATRIX;
-    sum->pair_passes = passes;
-  }
+  if (sum) form.fill(sum, prep, cnt, passes);
   return GG_OK;
 }
 
-// The route of a border call of n >= 2 rows, n_old < n, by the context's pairs
-// path.  DEFAULT: nothing is run.  MATRIX: the border positions part, or
-// GG_ERR_INVALID_ARG when the limits fail.  AUTO: the positions part when the
-// limits hold, and the product iff there is a column and index_reads > R *
-// chunk_rounds (R: GALAHGPU_PAIRS_MATRIX_RATIO, by default a border's own
-// 1,000).
-gg_status border_route(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
-                       uint32_t n_old, hipStream_t st, bool* matrix, MatrixPrep* prep) {
-  *matrix = false;
-  if (c->pairs_path == GG_PAIRS_PATH_DEFAULT) return GG_OK;
-  const bool fits = matrix::border_limits_ok(n, n_old, c->s);
-  if (c->pairs_path == GG_PAIRS_PATH_MATRIX && !fits)
-    return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 sketch slots or tile pairs, or more, on the matrix path");
-  if (!fits) return GG_OK;
-  const gg_status r = matrix_prepare(c, who, d_sk, d_lens, n, nullptr, n, prep, st, n_old);
-  if (r != GG_OK) return r;
-  gg_pairs_matrix_summary ms{};
-  fill_border_summary(&ms, *prep, n_old);
-  *matrix = c->pairs_path == GG_PAIRS_PATH_MATRIX ||
-            (prep->n_columns > 0 && (double)ms.index_reads > pairs_matrix_ratio(kBorderMatrixRatio) * (double)ms.chunk_rounds);
-  return GG_OK;
+// gg_pairs_matrix behind its context lookup
+gg_status pairs_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
+                           uint32_t m, float min_ani, gg_pair** out, uint64_t* n_out, gg_pairs_matrix_summary* sum) {
+  const std::string who = "gg_pairs_matrix";
+  if (!out || !n_out) return fail(c, GG_ERR_INVALID_ARG, who + ": null argument");
+  *out = nullptr;
+  *n_out = 0;
+  if (std::isnan(min_ani)) return fail(c, GG_ERR_INVALID_ARG, who + ": min_ani is NaN");
+  std::string err;
+  gg_status st = check_sketch_arrays(who, sketches, lens, n, rows, false, m, err);
+  if (st != GG_OK) return fail(c, st, err);
+  if (!matrix::pair_limits_ok(m, c->s) || !matrix::pair_limits_ok(n, c->s))
+    return fail(c, GG_ERR_INVALID_ARG, who + ": 2^31 sketch slots or tile pairs, or more");
+  st = check_sketch_rows(who, lens, n, c->s, rows, m, true, err);
+  if (st != GG_OK) return fail(c, st, err);
+  return pairs_form_host(c, who.c_str(), PairsForm{m, false, 0}, sketches, lens, n, rows, min_ani, out, n_out, sum);
+}
+
+// gg_pairs_border_matrix behind its context lookup
+gg_status pairs_border_matrix_ctx(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
+                                  float min_ani, gg_pair** out, uint64_t* n_out, gg_pairs_matrix_summary* sum) {
+  const std::string who = "gg_pairs_border_matrix";
+  if (!out || !n_out) return fail(c, GG_ERR_INVALID_ARG, who + ": null argument");
+  *out = nullptr;
+  *n_out = 0;
+  if (std::isnan(min_ani)) return fail(c, GG_ERR_INVALID_ARG, who + ": min_ani is NaN");
+  if (n_old > n) return fail(c, GG_ERR_INVALID_ARG, who + ": n_old exceeds n");
+  if (!matrix::border_limits_ok(n, n_old, c->s))
+    return fail(c, GG_ERR_INVALID_ARG, who + ": 2^31 sketch slots or tile pairs, or more");
+  std::string err;
+  gg_status st = check_sketch_arrays(who, sketches, lens, n, nullptr, false, n, err);
+  if (st == GG_OK) st = check_sketch_rows(who, lens, n, c->s, nullptr, n, false, err);
+  if (st != GG_OK) return fail(c, st, err);
+  return pairs_form_host(c, who.c_str(), PairsForm{n, true, n_old}, sketches, lens, n, nullptr, min_ani, out, n_out, sum);
 }
 
 }  // namespace
@@ -390,15 +263,52 @@ void count_pairs_path(gg_ctx* c, bool matrix) {
   ++c->pairs_paths_taken[!matrix ? 0 : c->pairs_path == GG_PAIRS_PATH_MATRIX ? 1 : 2];
 }
 
+gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                            float min_ani, gg_pair** d_pairs, uint64_t* n_pairs, uint32_t* n_passes, hipStream_t st,
+                            gg_pairs_matrix_summary* msum) {
+  *d_pairs = nullptr;
+  *n_pairs = 0;
+  *n_passes = 0;
+  if (msum) *msum = gg_pairs_matrix_summary{};
+  if (n < 2) return GG_OK;
+  const PairsForm form{n, false, 0};
+  const uint64_t all = form.all();
+  const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all);
+  // the matrix: by request, or by AUTO's rule from the counts of the positions part
+  bool matrix = false;
+  MatrixPrep prep{};
+  gg_pairs_matrix_summary ms{};
+  gg_status r = matrix_route(c, who, form, d_sk, d_lens, n, st, &matrix, &prep, &ms);
+  if (r != GG_OK) return r;
+  r = sized_pair_passes(
+      c, who, "rs_pairs", all, cap,
+      [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) {
+        return matrix ? form.run(c, d_sk, prep, min_ani, d_out, pcap, d_count, st)
+                      : pairs_core(c, d_sk, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, pcap, d_count, st);
+      },
+      d_pairs, n_pairs, n_passes, st);
+  if (r != GG_OK) return r;
+  count_pairs_path(c, matrix);
+  if (msum) {
+    *msum = ms;
+    msum->n_pairs = *n_pairs;
+    msum->path = matrix ? GG_PAIRS_PATH_MATRIX : GG_PAIRS_PATH_DEFAULT;
+    msum->pair_passes = *n_passes;
+  }
+  return GG_OK;
+}
+
 gg_status border_routed_to_host(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                                 uint32_t n_old, float min_ani, std::vector<gg_pair>& res, bool* ran, hipStream_t st) {
+  const PairsForm form{n, true, n_old};
   MatrixPrep prep{};
-  gg_status r = border_route(c, who, d_sk, d_lens, n, n_old, st, ran, &prep);
+  gg_pairs_matrix_summary ms{};
+  gg_status r = matrix_route(c, who, form, d_sk, d_lens, n, st, ran, &prep, &ms);
   if (r != GG_OK || !*ran) return r;
   gg_pair* d_sorted = nullptr;
   uint64_t cnt = 0;
   uint32_t passes = 0;
-  r = border_matrix_sorted(c, who, d_sk, prep, n, n_old, min_ani, &d_sorted, &cnt, &passes, st);
+  r = pairs_form_sorted(c, who, form, d_sk, prep, n, min_ani, &d_sorted, &cnt, &passes, st);
   if (r != GG_OK) return r;
   const size_t at = res.size();
   res.resize(at + cnt);
@@ -410,13 +320,12 @@ gg_status border_routed_to_host(gg_ctx* c, const char* who, const uint64_t* d_sk
 gg_status border_routed_append(gg_ctx* c, const char* who, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
                                uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count, bool* ran,
                                hipStream_t st) {
+  const PairsForm form{n, true, n_old};
   MatrixPrep prep{};
-  gg_status r = border_route(c, who, d_sk, d_lens, n, n_old, st, ran, &prep);
+  gg_pairs_matrix_summary ms{};
+  const gg_status r = matrix_route(c, who, form, d_sk, d_lens, n, st, ran, &prep, &ms);
   if (r != GG_OK || !*ran) return r;
-  uint32_t *d_cmin, *d_sufmin;
-  r = pairs_tables(c, min_ani, &d_cmin, &d_sufmin, st);
-  if (r != GG_OK) return r;
-  return pairs_border_matrix_launch(c, d_sk, prep, n - n_old, d_cmin, d_sufmin, d_out, cap, d_count, st);
+  return form.run(c, d_sk, prep, min_ani, d_out, cap, d_count, st);
 }
 
 gg_status cluster_rows_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, float min_ani,
@@ -481,13 +390,11 @@ gg_status gg_cluster_rows_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
   else
     st = cluster_rows_device(m, d_sketches, d_lens, n, min_ani, cluster_ani, d_rep_of, summary, d_pairs, d_ani,
                              (hipStream_t)stream);
-  if (st != GG_OK) {
+  return finish_call(ctx, m, st, [&] {
     if (summary) *summary = gg_cluster_summary{};
     if (d_pairs) *d_pairs = nullptr;
     if (d_ani) *d_ani = nullptr;
-    if (m != ctx) ctx->err = m->err;
-  }
-  return st;
+  });
 }
 
 gg_status gg_pairs_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
@@ -506,13 +413,22 @@ gg_status gg_pairs_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
   else if (hipSetDevice(pm->device) != hipSuccess)
     st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
   else
-    st = pairs_matrix_device(pm, d_sketches, d_lens, n, d_rows, m, min_ani, d_out, out_cap, d_count, summary,
-                             (hipStream_t)stream);
-  if (st != GG_OK) {
+    st = pairs_form_device(pm, "gg_pairs_matrix", PairsForm{m, false, 0}, d_sketches, d_lens, n, d_rows, min_ani, d_out,
+                           out_cap, d_count, summary, (hipStream_t)stream);
+  return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_pairs_matrix_summary{}; });
+}
+
+// the failure tail of the host forms: the list is freed, nothing is reported
+static gg_status finish_pair_list(gg_ctx* ctx, gg_ctx* pm, gg_status st, gg_pair** out, uint64_t* n_out,
+                                  gg_pairs_matrix_summary* summary) {
+  return finish_call(ctx, pm, st, [&] {
+    if (out) {
+      free(*out);
+      *out = nullptr;
+    }
+    if (n_out) *n_out = 0;
     if (summary) *summary = gg_pairs_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  });
 }
 
 gg_status gg_pairs_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
@@ -520,17 +436,8 @@ gg_status gg_pairs_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t*
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* pm = primary(ctx);
   if (summary) *summary = gg_pairs_matrix_summary{};
-  const gg_status st = pairs_matrix_ctx(pm, sketches, lens, n, rows, m, min_ani, out, n_out, summary);
-  if (st != GG_OK) {
-    if (out) {
-      free(*out);
-      *out = nullptr;
-    }
-    if (n_out) *n_out = 0;
-    if (summary) *summary = gg_pairs_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  return finish_pair_list(ctx, pm, pairs_matrix_ctx(pm, sketches, lens, n, rows, m, min_ani, out, n_out, summary), out,
+                          n_out, summary);
 }
 
 gg_status gg_pairs_border_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
@@ -549,18 +456,12 @@ gg_status gg_pairs_border_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches,
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: 2^31 sketch slots or tile pairs, or more");
   else if (work && (!d_sketches || !d_lens || !d_count || (out_cap && !d_out)))
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: null buffer");
-  else if (!work) {  // no pair: nothing is run, the count is left as it is
-    if (summary) summary->path = GG_PAIRS_PATH_MATRIX;
-  } else if (hipSetDevice(pm->device) != hipSuccess)
+  else if (work && hipSetDevice(pm->device) != hipSuccess)
     st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  else
-    st = pairs_border_matrix_device(pm, d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count, summary,
-                                    (hipStream_t)stream);
-  if (st != GG_OK) {
-    if (summary) *summary = gg_pairs_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  else  // (no work: nothing is run, the count is left as it is)
+    st = pairs_form_device(pm, "gg_pairs_border_matrix", PairsForm{n, true, n_old}, d_sketches, d_lens, n, nullptr, min_ani,
+                           d_out, out_cap, d_count, summary, (hipStream_t)stream);
+  return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_pairs_matrix_summary{}; });
 }
 
 gg_status gg_pairs_border_matrix(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t n_old,
@@ -568,17 +469,8 @@ gg_status gg_pairs_border_matrix(gg_ctx* ctx, const uint64_t* sketches, const ui
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* pm = primary(ctx);
   if (summary) *summary = gg_pairs_matrix_summary{};
-  const gg_status st = pairs_border_matrix_ctx(pm, sketches, lens, n, n_old, min_ani, out, n_out, summary);
-  if (st != GG_OK) {
-    if (out) {
-      free(*out);
-      *out = nullptr;
-    }
-    if (n_out) *n_out = 0;
-    if (summary) *summary = gg_pairs_matrix_summary{};
-    if (pm != ctx) ctx->err = pm->err;
-  }
-  return st;
+  return finish_pair_list(ctx, pm, pairs_border_matrix_ctx(pm, sketches, lens, n, n_old, min_ani, out, n_out, summary), out,
+                          n_out, summary);
 }
 
 gg_status gg_set_pairs_path(gg_ctx* ctx, int path) {
