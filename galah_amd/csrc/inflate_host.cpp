@@ -522,18 +522,26 @@ gg_status inflate_plan(gg_ctx* m, const uint8_t* h_in, uint64_t in_bytes, std::v
   // every unit: its last lane decoded the final block, ending at its
   // trailer, and the output length agrees with ISIZE
   std::vector<uint64_t> ulen(nu, 0), lane_out(live.size());
+  bool split_last = false;
   for (size_t l = 0; l < live.size(); ++l) {
     const uint32_t u = live[l].unit;
     lane_out[l] = ulen[u];
     ulen[u] += live[l].out_len;
     if (l + 1 == live.size() || live[l + 1].unit != u) {
+      // the unit's last lane ran into a member boundary: every such unit of
+      // the batch is split in this plan (one plan per unit ran a batch of
+      // more than six small concatenated files out of plans, to the host)
       if (live[l].bfin && (live[l].last_end + 7) / 8 < units[u].b1 / 8 && split_member(u, live[l].last_end)) {
-        *o = kReplan;  // (the unit's last lane ran into a member boundary)
-        return GG_OK;
+        split_last = true;
+        continue;
       }
       if (!live[l].bfin || (live[l].last_end + 7) / 8 != units[u].b1 / 8) return hand_back(o, "member end", u);
       if ((uint32_t)ulen[u] != units[u].isize) return hand_back(o, "ISIZE", u);
     }
+  }
+  if (split_last) {
+    *o = kReplan;
+    return GG_OK;
   }
   // text: each file's members one after the other, every file on a 16-byte
   // boundary (the gaps '\n')

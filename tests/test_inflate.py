@@ -11,7 +11,10 @@ genomes and for streams of every block type and zlib strategy.
 GPU: sketches and pairs with the device inflate equal the host path and the
 committed golden table; the cases it hands back to the host (several gzip
 members, FASTQ, a corrupt stream) give the host path's result or error and
-are counted."""
+are counted.
+
+Every stream here was written by zlib's compressor; the DEFLATE and gzip
+forms it never writes are in tests/test_inflate_foreign.py."""
 import gzip
 import json
 import os
