@@ -311,7 +311,6 @@ struct InflatePlace {
                                // a byte of the 32 KB before the lane's first byte
   uint32_t* flags;             // bit 0: a distance before its file's start,
                                // bit 2: a lane's tokens make other than lane_len bytes
-  uint64_t* prof = nullptr;    // (debug) expand cycles: fill, pointer rounds, write-out; steps, rounds
 };
 constexpr uint16_t kSymPtr = 0x8000u;
 // one file of an inflate batch (inflate_host.cpp): its bytes at
@@ -348,9 +347,6 @@ bool gzip_member(const uint8_t* buf, size_t n, size_t* data_off, size_t* data_le
 // flags, or does not end within buf and before the trailer.
 bool gzip_header(const uint8_t* buf, size_t n, uint64_t file_size, size_t* data_off);
 hipError_t launch_inflate_search(const InflateSearch& a, hipStream_t st);
-// bytes from mapped pinned host memory (its device address) to dst by a
-// kernel on st (inflate.hip); both buffers hold a multiple of 16 bytes
-hipError_t launch_slot_upload(uint8_t* dst, const uint8_t* src_mapped, uint64_t bytes, hipStream_t st);
 hipError_t launch_inflate_decode(const InflateDecode& a, hipStream_t st);
 // the text of a batch: expand (every lane's tokens into sym), then resolve
 // (each unit's lanes in order into text, the padding after a file's last

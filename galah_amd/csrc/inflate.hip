@@ -7,19 +7,21 @@
 // DEFLATE is serial within a stream, so the parallel units are the stream's
 // blocks (zlib level 6: ~16k symbols, ~100 KB of FASTA each; a 3 Mbp genome
 // has ~30 of them).  Kernels (inflate_core.hpp has the bit-level decoding):
-//   inflate_search_kernel   one wave per ~4 KB chunk of compressed data: the
+//   inflate_search_kernel   one wave per 48 KB chunk of compressed data: the
 //                           first bit position where a dynamic block header
-//                           parses (64 positions per step, one per lane)
+//                           parses (steps of 4,096 positions, 64 per lane)
 //   inflate_decode_kernel   one wave per found start: each block's header
 //                           by lane 0, its body split into 64 sub-spans
 //                           decoded at once and chained by resynchronisation
 //                           (inflate_core.hpp decode_span) into tokens, until
 //                           landing on the next start
-//   inflate_expand_kernel   one workgroup per segment, in order: token output
-//                           offsets by a block scan, the bytes of each step
-//                           built in LDS (back-references inside the segment
-//                           copied, those before it left as pointers into
-//                           the 32 KB before the segment): u16 per byte
+//   inflate_expand_kernel   one workgroup per segment, in order, three tokens
+//                           per thread and step: token output offsets by a
+//                           block scan, the bytes of each step built in LDS
+//                           (back-references inside the segment copied from
+//                           an LDS ring of its last 32 KB, those before it
+//                           left as pointers into the 32 KB before the
+//                           segment): u16 per byte
 //   inflate_resolve_kernel  one workgroup per gzip member, its segments in
 //                           order: the member's last 32 KB of text in an LDS
 //                           ring, so every pointer is one LDS read
@@ -27,9 +29,6 @@
 //   inflate_crc_fold_kernel per file its segments' CRCs folded with x^(8n)
 //                           mod P; checked with ISIZE against the gzip
 //                           trailer by the host
-#include <cstdlib>
-#include <cstring>
-
 #include "device_util.hpp"
 #include "gg_internal.hpp"
 #include "inflate_core.hpp"
@@ -52,49 +51,34 @@ struct ClLds {
 constexpr int kSearchWaves = 4;         // chunks per search workgroup (one wave each)
 constexpr uint32_t kSearchStep = 4096;  // positions per step: 64 consecutive per lane
 constexpr uint32_t kSearchCands = 256;  // candidates listed at most (more: the scan resumes after the last listed)
-#ifndef GG_CHECK_AT  // (A/B builds: -DGG_CHECK_AT=...)
-#define GG_CHECK_AT 48
-#endif
-constexpr uint32_t kCheckAt = GG_CHECK_AT;  // candidates that trigger a round of full checks (~1 per 1,100 positions)
-#ifndef GG_CHECK_STEPS  // (A/B builds; 1,000 C2-like files: 1 step per round (round 5) 9.08 ms, 4 8.14, 8 7.91, 32 7.78)
-#define GG_CHECK_STEPS 32
-#endif
-constexpr uint32_t kCheckSteps = GG_CHECK_STEPS;  // header-walk symbols per round of the checks' bookkeeping
+constexpr uint32_t kCheckAt = 48;  // candidates that trigger a round of full checks (~1 per 1,100 positions)
+// header-walk symbols per round of the checks' bookkeeping (1,000 C2-like
+// files: 1 step per round (round 5) 9.08 ms, 4 8.14, 8 7.91, 32 7.78)
+constexpr uint32_t kCheckSteps = 32;
 constexpr uint32_t kWinWords = kSearchStep / 32 + 8;  // a step's bits plus the 160 after its first lane's last
-#ifndef GG_CHK_LDS  // (A/B builds: -DGG_CHK_LDS=1, a round's stream copied to LDS first: search 7.7 -> 8.8-9.0 ms per 600 C2-like files)
-#define GG_CHK_LDS 0
-#endif
-constexpr uint32_t kChkWords = GG_CHK_LDS ? 2048 : 1;  // the stream from a check round's first candidate on, in LDS (~48 candidates span ~1,700)
 
-// The stream as a lane's full check reads it: words [wb, wb + nw) from the
-// LDS copy (one coalesced copy per round), the rest (a walk that runs past
-// it) from global memory, through a register window of three words that a
-// walk moving on by a word shifts, loading the word after it -- which it
-// needs a few symbols later -- so a code-length symbol waits on no stream
-// read (a round of checks is one walk of a real header, ~300 dependent
-// symbols long).
+// The stream as a lane's full check reads it: global memory through a
+// register window of three words that a walk moving on by a word shifts,
+// loading the word after it -- which it needs a few symbols later -- so a
+// code-length symbol waits on no stream read (a round of checks is one walk
+// of a real header, ~300 dependent symbols long).  (A round's stream copied
+// to LDS first, one coalesced copy, measured slower: search 7.7 -> 8.8-9.0
+// ms per 600 C2-like files.)
 struct WinBits {
-  const uint32_t* lds;
   const uint32_t* g;
-  uint64_t wb;
-  uint32_t nw;
   mutable uint64_t wi = ~0ull;  // the window's first word
   mutable uint32_t a = 0, b = 0, c = 0;
-  __device__ uint32_t word(uint64_t w) const {
-    const uint64_t i = w - wb;  // (w < wb wraps to the global read)
-    return i < nw ? lds[i] : g[w];
-  }
   __device__ uint32_t peek(uint64_t pos) const {
     const uint64_t w = pos >> 5;
     if (w != wi) {
       if (w == wi + 1) {
         a = b;
         b = c;
-        c = word(w + 2);
+        c = g[w + 2];
       } else {
-        a = word(w);
-        b = word(w + 1);
-        c = word(w + 2);
+        a = g[w];
+        b = g[w + 1];
+        c = g[w + 2];
       }
       wi = w;
     }
@@ -145,7 +129,6 @@ __device__ __forceinline__ uint64_t quick64(const uint32_t (&A)[5], const uint8_
 __global__ __launch_bounds__(64 * kSearchWaves, 4) void inflate_search_kernel(InflateSearch a) {
   __shared__ uint64_t cand[kSearchWaves][kSearchCands];
   __shared__ uint32_t win[kSearchWaves][kWinWords];
-  __shared__ uint32_t chk[kSearchWaves][kChkWords];
   __shared__ ClLds cls[kSearchWaves][64];
   __shared__ uint8_t kraft3[512];  // sum over 3 code-length fields of 128 >> len (0 for len 0)
   for (uint32_t i = threadIdx.x; i < 512; i += 64 * kSearchWaves) {
@@ -231,13 +214,7 @@ __global__ __launch_bounds__(64 * kSearchWaves, 4) void inflate_search_kernel(In
     }
     // the full checks of the listed candidates, in order
     if (a.prof && lane == 0) atomicAdd((unsigned long long*)&a.prof[4], (unsigned long long)nc);
-    WinBits wbits{chk[wv], stream, 0, 0};
-    if (GG_CHK_LDS && nc) {  // the stream from the first candidate on into LDS (the words the filter may read: up to wend)
-      wbits.wb = cw[0] >> 5;
-      wbits.nw = wend > wbits.wb ? (uint32_t)min<uint64_t>(kChkWords, wend - wbits.wb) : 0u;
-      for (uint32_t i = lane; i < wbits.nw; i += 64) chk[wv][i] = stream[wbits.wb + i];
-      __builtin_amdgcn_wave_barrier();
-    }
+    WinBits wbits{stream};
     // (each lane walks one candidate a symbol per step and takes the next
     // unclaimed one when its own is decided; done when a candidate passed
     // and none before it is still walking, or all are decided)
@@ -604,10 +581,7 @@ __device__ __forceinline__ uint32_t decode_span_lds(const uint32_t* lds, uint64_
 // segment's tokens, kCopyBatch loads in flight (a plain loop waited on each
 // load in turn; with 8 in flight a window's ~85 tokens per lane still took
 // ~11 waits: 16% of the decode)
-#ifndef GG_COPY_BATCH  // (A/B builds: -DGG_COPY_BATCH=8)
-#define GG_COPY_BATCH 32
-#endif
-constexpr uint32_t kCopyBatch = GG_COPY_BATCH;
+constexpr uint32_t kCopyBatch = 32;
 // Returns the bytes the tokens stand for (the decodes count no bytes).
 __device__ uint32_t copy_tokens(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t n) {
   uint32_t i = 0, bytes = 0;
@@ -653,9 +627,7 @@ __device__ uint32_t copy_tokens(uint32_t* __restrict__ dst, const uint32_t* __re
 // only.  Read from global memory, every cursor refill waited for its load
 // (the window rotation copies the loaded registers at once), a latency of
 // thousands of cycles every ~2.5 symbols.
-#ifndef GG_DECODE_MIN_WAVES
-#define GG_DECODE_MIN_WAVES 1
-#endif
+constexpr int kDecodeMinWaves = 1;  // (the launch bound's waves per SIMD)
 // (10 KB + the static tables ~10 KB: eight waves per CU, two per SIMD as the
 // 174 VGPRs allow; a zlib -6 block of FASTA, 24-27 KB, takes three windows.
 // C2 files per call: 30 KB stages (one wave per SIMD) 0.063-0.064 s, 18 KB
@@ -664,12 +636,10 @@ __device__ uint32_t copy_tokens(uint32_t* __restrict__ dst, const uint32_t* __re
 #ifndef GG_STAGE_KB
 #define GG_STAGE_KB 10
 #endif
+static_assert(GG_STAGE_KB >= 1 && GG_STAGE_KB <= 40, "the stage and the ~10 KB of static tables stay within 64 KB of LDS");
 constexpr uint32_t kStageWords = GG_STAGE_KB * 1024 / 4;
-#ifndef GG_CK_FLAT  // (A/B builds: -DGG_CK_FLAT=0, the first decode's checkpoints behind a branch)
-#define GG_CK_FLAT 1
-#endif
 template <bool kStaged>
-__global__ __launch_bounds__(kSpanLanes, GG_DECODE_MIN_WAVES) void inflate_decode_kernel(InflateDecode a) {
+__global__ __launch_bounds__(kSpanLanes, kDecodeMinWaves) void inflate_decode_kernel(InflateDecode a) {
   extern __shared__ uint32_t stage[];  // (kStaged: kStageWords words)
   __shared__ uint32_t llm[kMaxBits + 1], dlm[kMaxBits + 1];
   __shared__ int32_t lb[kMaxBits + 1], db[kMaxBits + 1];
@@ -808,11 +778,7 @@ __global__ __launch_bounds__(kSpanLanes, GG_DECODE_MIN_WAVES) void inflate_decod
         // first checkpoint are dropped as before)
         const uint64_t S0 = j == 0 ? S : (S - bstart > kWarmBits ? S - kWarmBits : bstart);
         uint64_t unused_bytes = 0;
-#if GG_CK_FLAT
         if constexpr (kStaged) sa = decode_span_lds<true>(stage, sbase, S0, S, R, tab, sink, ck1f, na, Ea);
-#else
-        if constexpr (kStaged) sa = decode_span_lds(stage, sbase, S0, S, R, tab, sink, ck1, na, Ea);
-#endif
         else sa = decode_span(in, S0, S, R, tab, sink, ck1, na, unused_bytes, Ea);
         sink.flush();
       }
@@ -963,48 +929,54 @@ __global__ __launch_bounds__(kSpanLanes, GG_DECODE_MIN_WAVES) void inflate_decod
 }
 
 // One workgroup per segment, its output built in order in steps of up to
-// kExpandThreads tokens / kExpandBytes bytes (this form, one token per
-// thread, is the A/B alternative, GG_EXPAND_TPT=1; the default,
-// inflate_expand2_kernel below, takes three tokens per thread and step and
-// the same ring).  The segment's last 32 KB of
+// kExpandThreads kTpt tokens / kTBytes bytes.  The segment's last 32 KB of
 // output stay in an LDS ring in sym's form (u16 per byte: a literal, or
 // kSymPtr | the position mod 32 KB of a byte before the segment), so every
 // back-reference inside the segment is an LDS read: a step's bytes are
 // staged (u16) as literals, pointers to before the segment (the segment
 // before is not expanded yet: the resolve pass follows them), ring values,
 // or kStepRef | the step byte they copy; kStepRef entries are followed
-// inside the step by pointer jumping, and the step goes to sym (coalesced)
-// and to the ring.  So a pointer left in sym reaches only into the 32 KB
-// before the segment, as the resolve's ring index.
+// inside the step, and the step goes to sym (coalesced) and to the ring.  So
+// a pointer left in sym reaches only into the 32 KB before the segment, as
+// the resolve's ring index.
 //
-// The tokens come from global memory kTokBuf at a time into LDS.  A wave
-// waits for a global load with every older global store of its own
-// outstanding (one counter for both, completed in order), and the step's
-// sym stores take ~25 us to complete: reading the next step's tokens from
-// global memory cost ~65k cycles per step against ~11k of work
-// (GALAHGPU_INFLATE_DEBUG with -DGG_EXPAND_PROF); with the LDS buffer one
-// step in four waits.  (Spreading a step's bytes over the threads instead of
-// its tokens measured slower: profiles/r06/expand_bytes_ab.txt.)
-// 512 threads and steps of <= 4000 bytes: 80 KB of LDS, two workgroups per
-// CU.  (A/B builds: scripts/ab_lib.sh with -DGG_EXPAND_THREADS=...
-// -DGG_EXPAND_BYTES=..., -DGG_EXPAND_PROF: the debug line's phase cycles)
-#ifndef GG_EXPAND_THREADS
-#define GG_EXPAND_THREADS 512
+// The tokens are prefetched into registers a step ahead.  A wave waits for a
+// global load with every older global store of its own outstanding (one
+// counter for both, completed in order), and the step's sym stores take ~25
+// us to complete: reading a step's tokens from global memory as the step
+// began cost ~65k cycles per step against ~11k of work.  (The LDS has no
+// room for a token buffer next to 16 KB of step bytes and the 64 KB ring:
+// 81,832 bytes, two workgroups per CU.  Spreading a step's bytes over the
+// threads instead of its tokens measured slower:
+// profiles/r06/expand_bytes_ab.txt.)
+//
+// 512 threads, three tokens per thread and step, steps of <= 8,000 bytes: a
+// third of the steps, barriers and scans of one token per thread.  1,000
+// C2-like files: 1 token per thread 13.9 ms, 2 (6,000-byte steps) 11.1,
+// 3 (8,000) 10.8, 4 (8,000) 12.1 (profiles/r06/expand_tpt_ab.txt).  (A/B
+// builds: scripts/ab_lib.sh with -DGG_EXPAND_TPT=... -DGG_EXPAND_TBYTES=...)
+constexpr int kExpandThreads = 512;
+#ifndef GG_EXPAND_TPT
+#define GG_EXPAND_TPT 3
 #endif
-#ifndef GG_EXPAND_BYTES
-#define GG_EXPAND_BYTES 4000
+#ifndef GG_EXPAND_TBYTES
+#define GG_EXPAND_TBYTES 8000
 #endif
-constexpr int kExpandThreads = GG_EXPAND_THREADS;
-constexpr uint32_t kExpandBytes = GG_EXPAND_BYTES;
-constexpr uint32_t kTokBuf = 4 * kExpandThreads - 128;  // tokens held in LDS (~4 steps of FASTA; the
-                                                        // total stays within 80 KB: two workgroups per CU)
+#ifndef GG_EXPAND_CHASE  // (hops per entry and round; 1: plain pointer jumping, measured slower)
+#define GG_EXPAND_CHASE 8
+#endif
+static_assert(GG_EXPAND_TPT >= 1 && GG_EXPAND_TPT <= 8, "tokens per thread and step");
+static_assert(GG_EXPAND_TBYTES >= 258 && GG_EXPAND_TBYTES <= 0x4000,
+              "a step holds the longest match, and its references are 14-bit");
+static_assert(GG_EXPAND_CHASE >= 1 && GG_EXPAND_CHASE <= 64, "hops per kStepRef entry and round");
+constexpr int kTpt = GG_EXPAND_TPT;
+constexpr uint32_t kTBytes = GG_EXPAND_TBYTES;
+constexpr int kChase = GG_EXPAND_CHASE;
 constexpr uint32_t kRing = 32768;       // the DEFLATE window
-constexpr uint16_t kStepRef = 0x4000u;  // step entry: the value of step byte (entry & 0x0FFF)
-static_assert(kExpandBytes <= 0x1000, "step bytes are 12-bit kStepRef indices");
+constexpr uint16_t kStepRef = 0x4000u;  // step entry: the value of step byte (entry & 0x3FFF)
 __global__ __launch_bounds__(kExpandThreads) void inflate_expand_kernel(InflatePlace a) {
-  __shared__ uint16_t v[kExpandBytes];
+  __shared__ uint16_t v[kTBytes];
   __shared__ uint16_t ring[kRing];
-  __shared__ uint32_t tb[kTokBuf];
   __shared__ uint32_t s_take, s_bytes;
   __shared__ uint32_t wsum[kExpandThreads / 64];
   const uint32_t seg = blockIdx.x;
@@ -1015,152 +987,6 @@ __global__ __launch_bounds__(kExpandThreads) void inflate_expand_kernel(InflateP
   const uint64_t f0 = a.file_text[a.lane_file[seg]];  // its unit's
   const uint64_t lim = o0 + a.lane_len[seg];           // (a corrupt stream's tokens may make more or fewer bytes
                                                        //  than the decode counted: nothing is written past lim)
-  uint64_t base = o0;
-  bool bad = false;
-  uint64_t tb0 = 0, tb1 = 0;  // tokens [tb0, tb1) are in tb
-#ifdef GG_EXPAND_PROF
-  uint64_t tp = a.prof ? clock64() : 0;
-  auto phase = [&](int k) {
-    if (a.prof) {
-      const uint64_t t = clock64();
-      if (tid == 0) atomicAdd((unsigned long long*)&a.prof[k], (unsigned long long)(t - tp));
-      tp = t;
-    }
-  };
-#else
-  auto phase = [](int) {};
-#endif
-  for (uint64_t t0 = 0; t0 < n;) {
-    if (t0 + kExpandThreads > tb1 && tb1 < n) {  // (uniform) the buffer from t0 on
-      tb0 = t0;
-      tb1 = min(n, t0 + kTokBuf);
-#pragma unroll
-      for (uint32_t k = 0; k < (kTokBuf + kExpandThreads - 1) / kExpandThreads; ++k) {
-        const uint64_t ti = t0 + tid + k * kExpandThreads;
-        if (ti < tb1) tb[tid + k * kExpandThreads] = tok[ti];
-      }
-      __syncthreads();
-    }
-    const uint64_t ti = t0 + tid;
-    const uint32_t tk = ti < n ? tb[(uint32_t)(ti - tb0)] : 0u;
-    const uint32_t len = ti < n ? tok_len(tk) : 0u;
-    uint32_t inc = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(inc, o);
-      if (ln >= (uint32_t)o) inc += y;
-    }
-    if (ln == 63) wsum[wave] = inc;
-    if (tid == 0) {
-      s_take = 0;
-      s_bytes = 0;
-    }
-    __syncthreads();
-    phase(5);
-    for (uint32_t w = 0; w < wave; ++w) inc += wsum[w];
-    const uint32_t before = inc - len;
-    const bool take = ti < n && inc <= kExpandBytes;  // (a prefix of the threads; thread 0 always)
-    const uint32_t c = (uint32_t)__popcll(__ballot(take));
-    const uint32_t last = __shfl(inc, c ? c - 1 : 0);  // this wave's bytes up to its last token taken
-    if (c && ln == 0) {
-      atomicAdd(&s_take, c);
-      atomicMax(&s_bytes, last);
-    }
-    if (take) {
-      if (!tok_is_match(tk)) {
-        v[before] = (uint16_t)(tk & 0xFFu);
-      } else {
-        const uint32_t dist = tok_dist(tk);
-        const uint64_t p = base + before;
-        if (p < f0 + dist) {
-          bad = true;  // a distance before the unit's first byte
-          for (uint32_t k = 0; k < len; ++k) v[before + k] = (uint16_t)'\n';
-        } else {
-          const uint64_t src = p - dist;
-          for (uint32_t k = 0; k < len; ++k) {
-            const uint64_t s = src + k;
-            uint16_t x;
-            if (s >= base) x = (uint16_t)(kStepRef | (uint32_t)(s - base));
-            else if (s < o0) x = (uint16_t)(kSymPtr | ((uint32_t)s & (kRing - 1)));
-            else x = ring[(uint32_t)s & (kRing - 1)];
-            v[before + k] = x;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    const uint32_t nb = s_bytes, nt = s_take;
-    phase(0);
-    for (;;) {  // kStepRef entries followed inside the step (each points to an earlier byte)
-#ifdef GG_EXPAND_PROF
-      if (a.prof && tid == 0) atomicAdd((unsigned long long*)&a.prof[4], 1ull);
-#endif
-      bool more = false;
-      for (uint32_t i = tid; i < nb; i += kExpandThreads) {
-        const uint32_t x = v[i];
-        if ((x & 0xC000u) == kStepRef) {
-          const uint32_t y = v[x & 0x0FFFu];
-          v[i] = (uint16_t)y;
-          more |= (y & 0xC000u) == kStepRef;
-        }
-      }
-      if (!__syncthreads_or(more)) break;
-    }
-    phase(1);
-    const uint32_t nw = base + nb <= lim ? nb : base < lim ? (uint32_t)(lim - base) : 0u;
-    for (uint32_t i = tid; i < nw; i += kExpandThreads) {
-      const uint16_t x = v[i];
-      a.sym[base + i] = x;
-      ring[(uint32_t)(base + i) & (kRing - 1)] = x;
-    }
-    __syncthreads();
-    phase(2);
-#ifdef GG_EXPAND_PROF
-    if (a.prof && tid == 0) atomicAdd((unsigned long long*)&a.prof[3], 1ull);
-#endif
-    base += nb;
-    t0 += nt;
-  }
-  if (bad) atomicOr(a.flags, 1u);
-  if (base != lim && tid == 0) atomicOr(a.flags, 4u);
-}
-
-#ifndef GG_EXPAND_TPT  // (A/B builds; 1,000 C2-like files: 1 token per thread 13.9 ms, 2 (6,000-byte steps) 11.1, 3 (8,000) 10.8, 4 (8,000) 12.1)
-#define GG_EXPAND_TPT 3
-#endif
-#ifndef GG_EXPAND_TBYTES  // (the step's bytes with GG_EXPAND_TPT > 1)
-#define GG_EXPAND_TBYTES 8000
-#endif
-#if GG_EXPAND_TPT > 1
-// The expand with kTpt tokens per thread and step (steps of up to 512 kTpt
-// tokens / kTBytes bytes: a third of the steps, barriers and scans per
-// segment of FASTA; 13.9 -> 10.8 ms per 1,000 C2-like files,
-// profiles/r06/expand_tpt_ab.txt); the tokens are prefetched into registers
-// a step ahead (the LDS has no room for a token buffer next to 16 KB of step
-// bytes and the 64 KB ring: 81,832 bytes, two workgroups per CU).
-constexpr int kTpt = GG_EXPAND_TPT;
-constexpr uint32_t kTBytes = GG_EXPAND_TBYTES;
-constexpr uint16_t kStepRef2 = 0x4000u;  // step entry: the value of step byte (entry & 0x3FFF)
-#ifndef GG_EXPAND_CHASE  // (A/B builds: -DGG_EXPAND_CHASE=1, plain pointer jumping)
-#define GG_EXPAND_CHASE 8
-#endif
-constexpr int kChase = GG_EXPAND_CHASE;
-#ifndef GG_EXPAND_FILL32  // (A/B builds: -DGG_EXPAND_FILL32=0, 64-bit positions and branches per byte)
-#define GG_EXPAND_FILL32 1
-#endif
-static_assert(kTBytes <= 0x4000, "14-bit step references");
-__global__ __launch_bounds__(kExpandThreads) void inflate_expand2_kernel(InflatePlace a) {
-  __shared__ uint16_t v[kTBytes];
-  __shared__ uint16_t ring[kRing];
-  __shared__ uint32_t s_take, s_bytes;
-  __shared__ uint32_t wsum[kExpandThreads / 64];
-  const uint32_t seg = blockIdx.x;
-  const uint32_t tid = threadIdx.x, ln = tid & 63u, wave = tid >> 6;
-  const uint32_t* tok = a.tok + a.tok_off[seg];
-  const uint64_t n = a.n_tok[seg];
-  const uint64_t o0 = a.lane_out[seg];
-  const uint64_t f0 = a.file_text[a.lane_file[seg]];
-  const uint64_t lim = o0 + a.lane_len[seg];
   const uint64_t nl = n ? n - 1 : 0;
   uint64_t base = o0;
   bool bad = false;
@@ -1175,11 +1001,10 @@ __global__ __launch_bounds__(kExpandThreads) void inflate_expand2_kernel(Inflate
     const uint32_t dist = tok_dist(tk);
     const uint64_t p = base + before;
     if (p < f0 + dist) {
-      bad = true;
+      bad = true;  // a distance before the unit's first byte
       for (uint32_t k = 0; k < len; ++k) v[before + k] = (uint16_t)'\n';
       return;
     }
-#if GG_EXPAND_FILL32
     // source bytes as 32-bit offsets from the step's first byte (r >= 0: in
     // the step; r < lo: before the lane), the ring read unconditionally and
     // the entry picked by selects (the 64-bit compares and branches per byte
@@ -1191,20 +1016,9 @@ __global__ __launch_bounds__(kExpandThreads) void inflate_expand2_kernel(Inflate
       const int32_t r = r0 + (int32_t)k;
       const uint32_t idx = (b32 + (uint32_t)r) & (kRing - 1);
       const uint32_t y = ring[idx];
-      const uint32_t x = r >= 0 ? (kStepRef2 | (uint32_t)r) : r < lo ? (kSymPtr | idx) : y;
+      const uint32_t x = r >= 0 ? (kStepRef | (uint32_t)r) : r < lo ? (kSymPtr | idx) : y;
       v[before + k] = (uint16_t)x;
     }
-#else
-    const uint64_t src = p - dist;
-    for (uint32_t k = 0; k < len; ++k) {
-      const uint64_t s = src + k;
-      uint16_t x;
-      if (s >= base) x = (uint16_t)(kStepRef2 | (uint32_t)(s - base));
-      else if (s < o0) x = (uint16_t)(kSymPtr | ((uint32_t)s & (kRing - 1)));
-      else x = ring[(uint32_t)s & (kRing - 1)];
-      v[before + k] = x;
-    }
-#endif
   };
   for (uint64_t t0 = 0; t0 < n;) {
     const uint64_t ti = t0 + (uint64_t)kTpt * tid;
@@ -1266,11 +1080,11 @@ __global__ __launch_bounds__(kExpandThreads) void inflate_expand2_kernel(Inflate
       bool more = false;
       for (uint32_t i = tid; i < nb; i += kExpandThreads) {
         uint32_t x = v[i];
-        if ((x & 0xC000u) == kStepRef2) {
+        if ((x & 0xC000u) == kStepRef) {
 #pragma unroll
-          for (int h = 0; h < kChase && (x & 0xC000u) == kStepRef2; ++h) x = v[x & 0x3FFFu];
+          for (int h = 0; h < kChase && (x & 0xC000u) == kStepRef; ++h) x = v[x & 0x3FFFu];
           v[i] = (uint16_t)x;
-          more |= (x & 0xC000u) == kStepRef2;
+          more |= (x & 0xC000u) == kStepRef;
         }
       }
       if (!__syncthreads_or(more)) break;
@@ -1288,7 +1102,6 @@ __global__ __launch_bounds__(kExpandThreads) void inflate_expand2_kernel(Inflate
   if (bad) atomicOr(a.flags, 1u);
   if (base != lim && tid == 0) atomicOr(a.flags, 4u);
 }
-#endif
 
 // One workgroup per unit (gzip member): its lanes' bytes in order, the
 // unit's last 32 KB of text in an LDS ring (position & 0x7FFF).  A lane's
@@ -1307,6 +1120,9 @@ __global__ __launch_bounds__(kExpandThreads) void inflate_expand2_kernel(Inflate
 #ifndef GG_RESOLVE_GROUPS
 #define GG_RESOLVE_GROUPS 2
 #endif
+static_assert(GG_RESOLVE_THREADS >= 64 && GG_RESOLVE_THREADS <= 1024 && GG_RESOLVE_THREADS % 64 == 0,
+              "whole waves, one workgroup");
+static_assert(GG_RESOLVE_GROUPS >= 1 && GG_RESOLVE_GROUPS <= 8, "16-byte groups per thread in flight");
 constexpr int kResolveThreads = GG_RESOLVE_THREADS;
 constexpr int kResolveGroups = GG_RESOLVE_GROUPS;  // 16-byte groups per thread in flight (their sym loads issued together)
 __global__ __launch_bounds__(kResolveThreads) void inflate_resolve_kernel(InflatePlace a) {
@@ -1557,80 +1373,9 @@ const CrcPowers& crc_powers() {
   return pw;
 }
 
-// A staged batch from its pinned host slot to the device (launch_slot_upload:
-// a DMA-engine copy; this kernel, GALAHGPU_GZ_UPLOAD=kernel, reads the
-// mapped slot over PCIe -- a few workgroups, each thread with four 16-byte
-// loads in flight -- and was the default until round 6, when its PCIe reads
-// were found to slow the kernels running beside it).
-constexpr int kUploadThreads = 256, kUploadBlocks = 64;
-template <bool kNt>
-__global__ __launch_bounds__(kUploadThreads) void slot_upload_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src,
-                                                                     uint64_t n16) {
-  const uint64_t stride = (uint64_t)gridDim.x * kUploadThreads;
-  uint64_t i = (uint64_t)blockIdx.x * kUploadThreads + threadIdx.x;
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-  auto ld = [&](uint64_t k) {
-    if (!kNt) return src[k];
-    const v4u v = __builtin_nontemporal_load((const v4u*)(src + k));
-    return make_uint4(v.x, v.y, v.z, v.w);
-  };
-  auto st = [&](uint64_t k, uint4 v) {
-    if (kNt) {
-      const v4u w = {v.x, v.y, v.z, v.w};
-      __builtin_nontemporal_store(w, (v4u*)(dst + k));
-    } else {
-      dst[k] = v;
-    }
-  };
-  for (; i + 3 * stride < n16; i += 4 * stride) {
-    const uint4 a = ld(i), b = ld(i + stride), c = ld(i + 2 * stride), d = ld(i + 3 * stride);
-    st(i, a);
-    st(i + stride, b);
-    st(i + 2 * stride, c);
-    st(i + 3 * stride, d);
-  }
-  for (; i < n16; i += stride) st(i, ld(i));
-}
-
 }  // namespace
 
 uint32_t inflate_stage_words() { return kStageWords; }
-
-hipError_t launch_slot_upload(uint8_t* dst, const uint8_t* src_mapped, uint64_t bytes, hipStream_t st) {
-  const uint64_t n16 = (bytes + 15) / 16;  // (both buffers are padded past bytes to a 16-byte multiple)
-  if (n16 == 0) return hipSuccess;
-  // A DMA-engine copy by default: the copy kernel's PCIe reads, running
-  // beside the other lane's kernels, slowed the latency-bound decode ~2x
-  // (a full batch's decode 1.65 ms alone, 4.5-4.8 ms beside the kernel;
-  // 600 C2-like files: decode 14.0 -> 6.6 ms per call, the call 0.038 ->
-  // 0.0315 s, profiles/r06/upload_ab.txt).  GALAHGPU_GZ_UPLOAD=kernel keeps the
-  // kernel (GALAHGPU_GZ_UPLOAD_BLOCKS, GALAHGPU_GZ_UPLOAD_NT=1: its workgroups,
-  // non-temporal accesses -- A/B knobs, read per call).
-  const char* mode = getenv("GALAHGPU_GZ_UPLOAD");
-  if (!(mode && strcmp(mode, "kernel") == 0)) {
-    // (GALAHGPU_GZ_UPLOAD_CHUNK_MB: the copy in pieces of that size, so that
-    // the lanes' small copies queued on the DMA engines behind it wait for one
-    // piece at most -- an A/B knob)
-    const char* ec = getenv("GALAHGPU_GZ_UPLOAD_CHUNK_MB");
-    const uint64_t chunk = ec && atoi(ec) > 0 ? (uint64_t)atoi(ec) << 20 : bytes;
-    for (uint64_t o = 0; o < bytes; o += chunk) {
-      const hipError_t e = hipMemcpyAsync(dst + o, src_mapped + o, std::min(chunk, bytes - o), hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  const char* eb = getenv("GALAHGPU_GZ_UPLOAD_BLOCKS");
-  const uint64_t want = eb && atoi(eb) > 0 ? (uint64_t)atoi(eb) : (uint64_t)kUploadBlocks;
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>(want, (n16 + kUploadThreads - 1) / kUploadThreads);
-  const char* nt = getenv("GALAHGPU_GZ_UPLOAD_NT");
-  if (nt && *nt == '1')
-    hipLaunchKernelGGL(slot_upload_kernel<true>, dim3(blocks), dim3(kUploadThreads), 0, st, (uint4*)dst,
-                       (const uint4*)src_mapped, n16);
-  else
-    hipLaunchKernelGGL(slot_upload_kernel<false>, dim3(blocks), dim3(kUploadThreads), 0, st, (uint4*)dst,
-                       (const uint4*)src_mapped, n16);
-  return hipGetLastError();
-}
 
 hipError_t launch_inflate_search(const InflateSearch& a, hipStream_t st) {
   if (a.n_chunks == 0) return hipSuccess;
@@ -1649,11 +1394,7 @@ hipError_t launch_inflate_decode(const InflateDecode& a, hipStream_t st) {
 }
 
 hipError_t launch_inflate_expand(const InflatePlace& a, hipStream_t st) {
-#if GG_EXPAND_TPT > 1
-  if (a.n_lanes) hipLaunchKernelGGL(inflate_expand2_kernel, dim3(a.n_lanes), dim3(kExpandThreads), 0, st, a);
-#else
   if (a.n_lanes) hipLaunchKernelGGL(inflate_expand_kernel, dim3(a.n_lanes), dim3(kExpandThreads), 0, st, a);
-#endif
   return hipGetLastError();
 }
 

@@ -504,10 +504,7 @@ struct HeaderWalk {
 // Decode entries: the value in bits 0..15 (a literal byte, a length base or
 // a distance base), its extra bits in 16..19, the code length in 20..23
 // (fast tables only; 0 = not in the table), the kind in 24..25.
-#ifndef GG_FAST_BITS  // (A/B builds: -DGG_FAST_BITS=9)
-#define GG_FAST_BITS 10
-#endif
-constexpr int kFastBits = GG_FAST_BITS;
+constexpr int kFastBits = 10;  // (the decode: an 11-bit table 27 ms against 20; 9 bits with more waves 11.9-12.8 against 10.4)
 constexpr uint32_t kFastSize = 1u << kFastBits;
 constexpr int kFastLenShift = 20;
 constexpr uint32_t kFastLenMask = 15u << kFastLenShift;

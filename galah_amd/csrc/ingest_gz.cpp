@@ -13,8 +13,8 @@
 // other pinned slot -- its pool of threads claims files one at a time from
 // the call's shared list (GzClaims), reads each straight into its place in
 // the slot (pread: no intermediate copy), and the batch goes to the slot's
-// device buffer by a kernel reading the mapped slot over PCIe.  A batch is cut at its size limits (the first batches of a call
-// smaller, so the GPU starts sooner); a claimed file that does not fit is
+// device buffer by one DMA-engine copy on the slot's stream.  A batch is cut
+// at its size limits (the first batches of a call smaller, so the GPU starts sooner); a claimed file that does not fit is
 // given back and claimed again first.
 //
 // A batch the device inflate does not take (a stream it cannot chain, a
@@ -229,7 +229,7 @@ struct GzStaged {
   std::string err;
   double ms = 0;
   Clock::time_point t0;
-  hipEvent_t up_a = nullptr, up_b = nullptr;  // (timing: the upload kernel)
+  hipEvent_t up_a = nullptr, up_b = nullptr;  // (timing: the upload copy)
 };
 
 // One lane's stager: two slots (pinned host + device buffers and an upload
@@ -431,15 +431,17 @@ class GzStager {
     for (int t = 1; t < threads_; ++t) th.emplace_back(worker);
     worker();
     for (auto& x : th) x.join();
-    // the batch to the device by a kernel reading the mapped slot (inflate.hip
-    // launch_slot_upload): no DMA-engine queue for the lanes' small copies to wait behind
+    // the batch to the device by one DMA-engine copy on the slot's stream (a
+    // kernel reading the mapped slot over PCIe, running beside the other
+    // lane's kernels, slowed the latency-bound decode ~2x: a full batch's
+    // decode 1.65 ms alone, 4.5-4.8 ms beside it, profiles/r06/upload_ab.txt)
     if (g.st == GG_OK && !g.file_err && g.at) {
       if (m_->timing && !g.up_a) {  // (events of the consuming lane's timing, gg_timing_read)
         hip(hipEventCreate(&g.up_a), "hipEventCreate");
         hip(hipEventCreate(&g.up_b), "hipEventCreate");
       }
       if (g.up_a) hip(hipEventRecord(g.up_a, sl.st), "hipEventRecord");
-      hip(launch_slot_upload(sl.dev, sl.host_dev, g.at, sl.st), "slot upload");
+      hip(hipMemcpyAsync(sl.dev, sl.host_dev, g.at, hipMemcpyHostToDevice, sl.st), "slot upload");
       if (g.up_b) hip(hipEventRecord(g.up_b, sl.st), "hipEventRecord");
     }
     g.ms = ms_since(g.t0);

@@ -1371,22 +1371,15 @@ hipError_t index_build_buckets(const IndexBuild& b, uint64_t total, uint32_t nb_
   }
   // the entries land in keys_in (free after the sort), as with the run pass
   const uint32_t per_xcd = (nb_bound + kXcds - 1) / kXcds;
-  // 1024 threads per bucket (GALAHGPU_BUCKET_THREADS=256|512: A/B; C5 index_bucket
-  // 1.76 ms at 256, 1.74 at 512, 1.63 at 1024)
-  const char* bt = getenv("GALAHGPU_BUCKET_THREADS");
-  const int threads = bt && *bt ? atoi(bt) : 1024;
-  auto go = [&](auto kern, int t) {
-    hipLaunchKernelGGL(kern, dim3(per_xcd * kXcds), dim3(t), 0, st, vout, b.bstart, nbuckets_d, total, b.sketches,
+  // 1024 threads per bucket (C5 index_bucket 1.76 ms at 256, 1.74 at 512,
+  // 1.63 at 1024)
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(per_xcd * kXcds), dim3(1024), 0, st, vout, b.bstart, nbuckets_d, total, b.sketches,
                        b.stride, b.kbits, b.max_run, b.runinfo, b.keys_in, index_ents16(b.n) ? 1u : 0u, b.flags,
                        b.cost, b.border ? b.border0 : 0u);
   };
-  if (b.border) {
-    if (threads == 256) go(index_bucket_kernel<256, true>, 256);
-    else if (threads == 512) go(index_bucket_kernel<512, true>, 512);
-    else go(index_bucket_kernel<1024, true>, 1024);
-  } else if (threads == 256) go(index_bucket_kernel<256, false>, 256);
-  else if (threads == 512) go(index_bucket_kernel<512, false>, 512);
-  else go(index_bucket_kernel<1024, false>, 1024);
+  if (b.border) go(index_bucket_kernel<1024, true>);
+  else go(index_bucket_kernel<1024, false>);
   hipError_t e2 = hipGetLastError();
   if (e2 != hipSuccess) return e2;
   hipLaunchKernelGGL(index_cost_sum_kernel, dim3(1), dim3(kCostSlots), 0, st, b.cost);

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Device-inflate ingest knobs A/B on C2-like files in one box call (each
-# setting twice, alternating): GALAHGPU_GZ_BATCH_MB, GALAHGPU_GZ_COPY_THREADS,
-# GALAHGPU_GZ_MMAP.  usage: scripts/inflate_ab.sh <outdir> "<setting>"...
+# setting twice, alternating): GALAHGPU_GZ_BATCH_MB, GALAHGPU_GZ_COPY_THREADS.
+# usage: scripts/inflate_ab.sh <outdir> "<setting>"...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 export TMPDIR=/tmp PROBE_MODES=device
 out=$1; shift

@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes over one device-inflate call on C2-like files (1,000 x 3 Mbp
-# gzip FASTA, scripts/inflate_probe.py) for every ingest kernel: the slot
-# upload, block-start search, staged and global decodes, expand, resolve,
+# gzip FASTA, scripts/inflate_probe.py) for every ingest kernel: the
+# block-start search, staged and global decodes, expand, resolve,
 # CRC, the three parse passes and K1.  One lane (GALAHGPU_GZ_LANES=1: the
 # kernels of two lanes would share the counters' time) and one rocprofv3 run
 # per counter set (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE each in a
@@ -12,7 +12,7 @@ export TMPDIR=/tmp PROBE_MODES=device GALAHGPU_GZ_LANES=1
 out=$1
 n=${2:-1000}
 mkdir -p "$out"
-rx='inflate_|parse_|slot_upload|sketch_candidates|sketch_finalize'
+rx='inflate_|parse_|sketch_candidates|sketch_finalize'
 sets=(
   "GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT"
   "GRBM_GUI_ACTIVE FETCH_SIZE"

@@ -27,7 +27,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import k2_pmc_model as km  # noqa: E402
 
-CLASSES = (("slot_upload", "upload"), ("inflate_search", "search"), ("inflate_decode_kernel<true>", "decode_staged"),
+CLASSES = (("inflate_search", "search"), ("inflate_decode_kernel<true>", "decode_staged"),
            ("inflate_decode_kernel<false>", "decode_global"), ("inflate_expand", "expand"),
            ("inflate_resolve", "resolve"), ("inflate_crc", "crc"), ("parse_", "parse"),
            ("sketch_candidates", "k1"), ("sketch_finalize", "k1_finalize"))

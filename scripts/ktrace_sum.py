@@ -6,7 +6,7 @@ import glob
 import os
 import sys
 
-CLASSES = (("slot_upload", "upload"), ("inflate_search", "search"), ("inflate_decode", "decode"),
+CLASSES = (("inflate_search", "search"), ("inflate_decode", "decode"),
            ("inflate_expand", "expand"), ("inflate_resolve", "resolve"), ("inflate_crc", "crc"),
            ("parse_", "parse"), ("sketch_candidates", "k1"), ("sketch_finalize", "k1"))
 root = sys.argv[1]
@@ -21,5 +21,5 @@ for d in sorted(glob.glob(os.path.join(root, "*")), key=os.path.getmtime):
             if key in r["Name"]:
                 ms[cls] = ms.get(cls, 0.0) + float(r["TotalDurationNs"]) / 1e6 / calls
                 break
-    dev = sum(v for k, v in ms.items() if k != "upload")
+    dev = sum(ms.values())
     print("%-14s " % os.path.basename(d) + " ".join("%s %.2f" % (k, ms[k]) for k in sorted(ms)) + "  | device %.2f" % dev)
