@@ -40,6 +40,7 @@ __all__ = [
     "pairs_border_host", "PreclusterState", "relabel_pairs", "cluster_update",
     "ani_matrix_host", "ani_matrix", "write_ani_matrix",
     "ani_matrix_group_cells", "ani_matrix_groups_host", "ani_matrix_block", "precluster_ani_matrices",
+    "Collection",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,6 +76,9 @@ EXPORTED_SYMBOLS = (
     "gg_pairs_matrix_device", "gg_pairs_matrix", "gg_pairs_border_matrix_device", "gg_pairs_border_matrix",
     "gg_set_pairs_path", "gg_pairs_path", "gg_pairs_paths_taken",
     "gg_precluster_files_resident",
+    "gg_collection_create", "gg_collection_destroy", "gg_collection_stat", "gg_collection_load",
+    "gg_collection_add_rows", "gg_collection_add_rows_device", "gg_collection_add_files", "gg_collection_remove",
+    "gg_collection_cluster", "gg_collection_pairs", "gg_collection_rows", "gg_collection_view",
 )
 
 GG_OK = 0
@@ -271,6 +275,31 @@ _sig("gg_pairs_paths_taken", _i32, [_vp, _vp])
 _sig("gg_precluster_files_resident", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
                                             ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                             ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
+
+
+class _CollectionInfo(ctypes.Structure):
+    _fields_ = [("n_pairs", ctypes.c_uint64), ("pair_capacity", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
+                ("n_rows", ctypes.c_uint32), ("row_capacity", ctypes.c_uint32), ("grows", ctypes.c_uint32),
+                ("rows_moved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+_sig("gg_collection_create", _i32, [_vp, ctypes.c_float, _u32, _u64, ctypes.POINTER(_vp)])
+_sig("gg_collection_destroy", None, [_vp])
+_sig("gg_collection_stat", _i32, [_vp, ctypes.POINTER(_CollectionInfo), ctypes.POINTER(ctypes.c_float)])
+_sig("gg_collection_load", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, ctypes.c_float, ctypes.POINTER(_vp)])
+_sig("gg_collection_add_rows", _i32, [_vp, _vp, _vp, _u32, ctypes.POINTER(_u64)])
+_sig("gg_collection_add_rows_device", _i32, [_vp, _vp, _vp, _u32, ctypes.POINTER(_u64), _vp])
+_sig("gg_collection_add_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p,
+                                       ctypes.POINTER(_u64)])
+_sig("gg_collection_remove", _i32, [_vp, _vp, _u32, _vp])
+_sig("gg_collection_cluster", _i32, [_vp, _vp, ctypes.c_float, _vp])
+_sig("gg_collection_pairs", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_collection_rows", _i32, [_vp, _vp, _vp])
+_sig("gg_collection_view", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                  ctypes.POINTER(_vp)])
 
 
 class _Validation(ctypes.Structure):
@@ -1112,6 +1141,123 @@ class Context:
         pairs, ani = self._pairs_ani(pp, ap, cnt.value)
         return out[:n_new], lens[:n_new], pairs, ani
 
+    # ---- a collection resident on the device (gg_collection_*; class Collection wraps a handle)
+    def collection_create(self, min_ani, reserve_rows=0, reserve_pairs=0):
+        """An empty resident collection at min_ani -> its handle (collection_destroy frees it)."""
+        h = _vp()
+        st = _L.gg_collection_create(self._c, ctypes.c_float(min_ani), int(reserve_rows), int(reserve_pairs),
+                                     ctypes.byref(h))
+        if st != GG_OK:
+            raise self._err(st)
+        return h.value
+
+    def collection_load(self, sketches, lens, pairs, ani, min_ani):
+        """A collection from saved rows, pairs sorted by (i, j) and their f32
+        ANI (checked for form, not recomputed) -> its handle."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        pa = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE).reshape(-1)
+        an = np.ascontiguousarray(ani, dtype=np.float32).reshape(-1)
+        if len(pa) != len(an):
+            raise ValueError("one ANI value per pair")
+        h = _vp()
+        st = _L.gg_collection_load(self._c, _ptr(sk), _ptr(ln), n, _ptr(pa), _ptr(an), len(pa),
+                                   ctypes.c_float(min_ani), ctypes.byref(h))
+        if st != GG_OK:
+            raise self._err(st)
+        return h.value
+
+    def collection_destroy(self, handle):
+        _L.gg_collection_destroy(handle)
+
+    def collection_stat(self, handle):
+        """-> ({n_pairs, pair_capacity, device_bytes, n_rows, row_capacity, grows, rows_moved}, min_ani f32)."""
+        info, thr = _CollectionInfo(), ctypes.c_float()
+        st = _L.gg_collection_stat(handle, ctypes.byref(info), ctypes.byref(thr))
+        if st != GG_OK:
+            raise _thread_err(st)
+        return info.as_dict(), np.float32(thr.value)
+
+    def collection_add_rows(self, handle, sketches, lens):
+        """Host rows appended -> the number of border pairs added."""
+        sk, ln, n_new, _ = _rows_arg(sketches, lens, self.s)
+        added = _u64()
+        st = _L.gg_collection_add_rows(handle, _ptr(sk), _ptr(ln), n_new, ctypes.byref(added))
+        if st != GG_OK:
+            raise self._err(st)
+        return added.value
+
+    def collection_add_rows_device(self, handle, d_sketches, d_lens, n_new, stream=None):
+        """Device rows (tensors or pointers) appended -> the number of border pairs added."""
+        added = _u64()
+        st = _L.gg_collection_add_rows_device(handle, _dev_ptr(d_sketches), _dev_ptr(d_lens), int(n_new),
+                                              ctypes.byref(added), stream)
+        if st != GG_OK:
+            raise self._err(st)
+        return added.value
+
+    def collection_add_files(self, handle, paths, cache_dir=None):
+        """Files sketched (cache_dir as sketch_files) and appended -> the number of border pairs added."""
+        n_new = len(paths)
+        arr = (ctypes.c_char_p * max(n_new, 1))(*[os.fsencode(p) for p in paths])
+        added = _u64()
+        st = _L.gg_collection_add_files(handle, arr, n_new, None if cache_dir is None else os.fsencode(cache_dir),
+                                        ctypes.byref(added))
+        if st != GG_OK:
+            raise self._err(st)
+        return added.value
+
+    def collection_remove(self, handle, rows):
+        """Rows (any order, repeats allowed) removed -> new_index [n before]
+        u32, 0xFFFFFFFF for a removed row."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        n = self.collection_stat(handle)[0]["n_rows"]
+        new_index = np.zeros(max(n, 1), np.uint32)
+        st = _L.gg_collection_remove(handle, _ptr(rows) if len(rows) else None, len(rows), _ptr(new_index))
+        if st != GG_OK:
+            raise self._err(st)
+        return new_index[:n]
+
+    def collection_cluster(self, handle, cluster_ani, order=None):
+        """rep_of [n] u32 (positions in order; order: position -> row, None: identity)."""
+        n = self.collection_stat(handle)[0]["n_rows"]
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
+            if len(order) != n:
+                raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
+        rep_of = np.zeros(max(n, 1), np.uint32)
+        st = _L.gg_collection_cluster(handle, None if order is None or n == 0 else _ptr(order),
+                                      ctypes.c_float(cluster_ani), _ptr(rep_of))
+        if st != GG_OK:
+            raise self._err(st)
+        return rep_of[:n]
+
+    def collection_pairs(self, handle):
+        """-> (pairs sorted by (i, j), ani f32)."""
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        st = _L.gg_collection_pairs(handle, ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        return self._pairs_ani(pp, ap, cnt.value)
+
+    def collection_rows(self, handle):
+        """-> (sketches [n, s] u64, lens [n] u32)."""
+        n = self.collection_stat(handle)[0]["n_rows"]
+        out = np.zeros((max(n, 1), self.s), dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        st = _L.gg_collection_rows(handle, _ptr(out), _ptr(lens))
+        if st != GG_OK:
+            raise self._err(st)
+        return out[:n], lens[:n]
+
+    def collection_view(self, handle):
+        """Device pointers (ints) of the sketches, lens, pairs and ANI, valid
+        until the next call that changes the collection."""
+        p = [_vp(), _vp(), _vp(), _vp()]
+        st = _L.gg_collection_view(handle, *[ctypes.byref(x) for x in p])
+        if st != GG_OK:
+            raise _thread_err(st)
+        return tuple(x.value or 0 for x in p)
+
     def sketch_files(self, paths, cache_dir=None):
         """finch sketch_files (src/finch.rs:47) for files -> (sketches [n, s] u64
         padded with 0, lens [n] u32, number of genomes served by cache_dir)."""
@@ -1879,6 +2025,12 @@ class FinchPreclusterer(PreclusterDistanceFinder):
                                 self.min_ani)
         return self.update(empty, genome_fasta_paths)
 
+    def collection(self, reserve=0):
+        """An empty Collection (resident on the GPU) with this preclusterer's
+        k, sketch size, min_ani, sketch cache directory and pairs path;
+        reserve: genomes to make room for at once."""
+        return Collection(self, reserve=reserve)
+
     def update(self, state, new_paths):
         """Adds genomes to a finished run -> a PreclusterState over state.paths
         + new_paths whose cache() equals distances(state.paths + new_paths):
@@ -2009,6 +2161,147 @@ def cluster_update(state, new_paths, preclusterer, clusterer, order=None):
     except GalahGpuError as e:
         raise RuntimeError("Failed to cluster genomes: %s" % e) from e
     return clusters_from_reps(rep_of), new_state
+
+
+class Collection:
+    """A set of genomes kept on the GPU between calls (gg_collection_*,
+    DESIGN.md 4.15): their sketches, the passing pairs at the preclusterer's
+    min_ani and their f32 ANI stay in device memory; add() reads and sketches
+    only the new files and evaluates only their border, remove() filters and
+    renumbers, cluster() relabels into any order and clusters.  Every result
+    equals what FinchPreclusterer.distances / cluster give from scratch on
+    .paths.  A context manager; FinchPreclusterer.collection() makes one."""
+
+    def __init__(self, preclusterer, reserve=0, _handle=None, _paths=()):
+        self._pre = preclusterer
+        self._ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
+        self._paths = list(_paths)
+        self._h = None
+        try:
+            self._h = _handle if _handle is not None else self._ctx.collection_create(
+                float(np.float32(preclusterer.min_ani)), reserve_rows=reserve, reserve_pairs=0)
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to make a collection: %s" % e) from e
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_c", None):  # (a handle outlives its context only at interpreter exit)
+                self._ctx.collection_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return len(self._paths)
+
+    @property
+    def paths(self):
+        return list(self._paths)
+
+    def info(self):
+        return self._ctx.collection_stat(self._h)[0]
+
+    def _routed(self, call):
+        """call() under the preclusterer's pairs path, as FinchPreclusterer.update routes its border."""
+        ctx, path = self._ctx, self._pre.pairs_path
+        if path is None or ctx.device_count != 1:
+            return call()
+        before = ctx.set_pairs_path(path)  # (the cached context is shared: put back what was set)
+        try:
+            return call()
+        finally:
+            ctx.set_pairs_path(before)
+
+    def add(self, paths):
+        """Adds genomes (files) -> the number of pairs added.  ValueError on a
+        path already present; a file that cannot be read or parsed leaves the
+        collection as it was."""
+        new = [os.fspath(p) for p in paths]
+        seen = set(self._paths)
+        for p in new:
+            if p in seen:
+                raise ValueError("genome already present: %s" % p)
+            seen.add(p)
+        try:
+            added = self._routed(lambda: self._ctx.collection_add_files(self._h, new,
+                                                                        cache_dir=self._pre.sketch_cache_dir))
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+        self._paths += new
+        return added
+
+    def remove(self, paths):
+        """Removes genomes by path (ValueError on one that is not present);
+        the others keep their relative order."""
+        index = {p: x for x, p in enumerate(self._paths)}
+        rows = []
+        for p in paths:
+            p = os.fspath(p)
+            if p not in index:
+                raise ValueError("genome not present: %s" % p)
+            rows.append(index[p])
+        new_index = self._ctx.collection_remove(self._h, rows)
+        self._paths = [p for x, p in enumerate(self._paths) if new_index[x] != 0xFFFFFFFF]
+
+    def cache(self):
+        """The pairs as FinchPreclusterer.distances(self.paths) returns them."""
+        pairs, ani = self._ctx.collection_pairs(self._h)
+        cache = SortedPairGenomeDistanceCache()
+        for p, a in zip(pairs, ani):
+            cache.insert((int(p["i"]), int(p["j"])), np.float32(a))
+        return cache
+
+    def cluster(self, clusterer, order=None):
+        """The clusters of the collection's genomes as cluster_update returns
+        them: lists of positions in `order` (position -> index into .paths;
+        None: the paths' order), each with its representative first."""
+        clusterer.initialise()
+        pre_name, clu_name = self._pre.method_name(), clusterer.method_name()
+        if not (pre_name == clu_name == "finch"):
+            raise NotImplementedError("galah_amd.Collection.cluster: only finch + finch runs here, not %s + %s"
+                                      % (pre_name, clu_name))
+        if order is not None:
+            order = np.asarray(order, dtype=np.int64).reshape(-1)
+            n = len(self._paths)
+            if len(order) != n or (n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n)):
+                raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
+        try:
+            rep_of = self._ctx.collection_cluster(self._h, float(np.float32(clusterer.get_ani_threshold())), order)
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to cluster genomes: %s" % e) from e
+        return clusters_from_reps(rep_of)
+
+    def state(self):
+        """A PreclusterState of the collection (save / load as ever)."""
+        sk, lens = self._ctx.collection_rows(self._h)
+        pairs, ani = self._ctx.collection_pairs(self._h)
+        return PreclusterState(self._paths, sk, lens, pairs, ani, self._pre.kmer_length, self._pre.num_kmers, 0,
+                               self._pre.min_ani)
+
+    @classmethod
+    def from_state(cls, state, preclusterer):
+        """A collection holding a PreclusterState (gg_collection_load: the
+        pairs are checked for form and trusted, not recomputed).  ValueError
+        when the state was made with another k, sketch size, seed or min_ani."""
+        mine = (preclusterer.kmer_length, preclusterer.num_kmers, 0, np.float32(preclusterer.min_ani).tobytes())
+        if (state.k, state.s, state.seed, np.float32(state.min_ani).tobytes()) != mine:
+            raise ValueError("PreclusterState of k=%d s=%d seed=%d min_ani=%r, preclusterer of k=%d s=%d seed=0 "
+                             "min_ani=%r" % (state.k, state.s, state.seed, state.min_ani, preclusterer.kmer_length,
+                                             preclusterer.num_kmers, preclusterer.min_ani))
+        ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
+        try:
+            h = ctx.collection_load(state.sketches, state.lens, state.pairs, state.ani,
+                                    float(np.float32(preclusterer.min_ani)))
+        except GalahGpuError as e:
+            raise ValueError("not a saved collection state: %s" % e) from e
+        return cls(preclusterer, _handle=h, _paths=state.paths)
 
 
 class ClusterDistanceFinder:

@@ -380,6 +380,45 @@ gg_status border_routed_append(gg_ctx* c, const char* who, const uint64_t* d_sk,
                                uint32_t n_old, float min_ani, gg_pair* d_out, uint64_t cap, uint64_t* d_count, bool* ran,
                                hipStream_t st);
 void count_pairs_path(gg_ctx* c, bool matrix);
+// The sized passes of a pair producer into scratch `key`: the first at `cap`,
+// one retry at the exact count.  run(d_out, cap, d_count) enqueues it on st.
+// (resident.cpp's calls and the collection's border, collection.cpp)
+template <typename Run>
+gg_status sized_pair_passes(gg_ctx* c, const std::string& who, const char* key, uint64_t all, uint64_t cap,
+                            const Run& run, gg_pair** d_pairs, uint64_t* n_pairs, uint32_t* n_passes, hipStream_t st) {
+  gg_pair* d_out = nullptr;
+  uint64_t cnt = 0;
+  uint32_t passes = 0;
+  uint64_t *d_count, *h_count;
+  GG_HIP(c, scratch_t(c, "rs_count", 1, &d_count));
+  GG_HIP(c, host_scratch_t(c, "rs_count", 1, &h_count));
+  for (;;) {
+    if (passes == 2) return fail(c, GG_ERR_INTERNAL, who + ": pair output sizing failed");
+    GG_HIP(c, scratch_t(c, key, (size_t)(cap > 1 ? cap : 1), &d_out));
+    GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+    const gg_status ps = run(d_out, cap, d_count);
+    if (ps != GG_OK) return ps;
+    ++passes;
+    GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    GG_HIP(c, hipStreamSynchronize(st));
+    cnt = *h_count;
+    if (cnt > all) return fail(c, GG_ERR_INTERNAL, who + ": bad pair count");
+    if (cnt <= cap) break;
+    cap = cnt;
+  }
+  if (cnt >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, who + ": 2^31 pairs or more");
+  *d_pairs = d_out;
+  *n_pairs = cnt;
+  *n_passes = passes;
+  return GG_OK;
+}
+// The rows of a file list on the first member's device (multi.cpp): sketched
+// by sketch_files_members (cache and errors as gg_sketch_files; a multi-device
+// context sketches on every member, the rows then go to the first through the
+// host, as gg_precluster_files_resident).  *d_sk / *d_len: context scratch of
+// the first member, valid until its next call.  Synchronises its stream.
+gg_status sketch_files_first(gg_ctx* ctx, const char* const* paths, uint32_t n, const char* cache_dir,
+                             const uint64_t** d_sk, const uint32_t** d_len);
 // Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
 // ani_f32_device, cluster_device; with sum, the partition of
 // preclusters_device.  *d_pairs / *d_ani (may be null) receive the scratch

@@ -482,6 +482,33 @@ hipError_t sort_pairs_device(const gg_pair* d_pairs, uint64_t cnt, uint32_t n, u
                              uint32_t* idx, uint32_t* idx_out, gg_pair* sorted, void* tmp, size_t tmp_bytes,
                              hipStream_t st);
 
+// collection.hip: the resident collection's kernels (collection_core.hpp; all
+// device pointers, counts < 2^31, row indices < n)
+// a_start / b_start [n + 1]: the row boundaries of two (i, j)-sorted lists
+hipError_t launch_collection_row_bounds(const gg_pair* a, uint32_t na, uint32_t* a_start, const gg_pair* b, uint32_t nb,
+                                        uint32_t* b_start, uint32_t n, hipStream_t st);
+// the old list (j < the first new row) and the sorted border of n rows merged
+// into out / out_ani [n_old + n_border]; old_pairs and out 16-byte aligned
+hipError_t launch_collection_merge(const gg_pair* old_pairs, const float* old_ani, uint32_t n_old, const gg_pair* border,
+                                   const float* border_ani, uint32_t n_border, const uint32_t* old_start,
+                                   const uint32_t* border_start, uint32_t n, gg_pair* out, float* out_ani,
+                                   hipStream_t st);
+// flags [cnt + 1]: both ends of the pair survive (new_index [n]); at [cnt + 1]:
+// their exclusive scan, at[cnt] the survivors
+size_t collection_scan_tmp_bytes(uint32_t cnt);
+hipError_t launch_collection_pair_scan(const gg_pair* pairs, uint32_t cnt, uint32_t n, const uint32_t* new_index,
+                                       uint32_t* flags, uint32_t* at, void* tmp, size_t tmp_bytes, hipStream_t st);
+hipError_t launch_collection_pair_compact(const gg_pair* pairs, const float* ani, uint32_t cnt, const uint32_t* new_index,
+                                          const uint32_t* flags, const uint32_t* at, uint32_t out_cap, gg_pair* out,
+                                          float* out_ani, hipStream_t st);
+// the kept rows among [src0, src1) into bounce slot new_index[r] - dst0
+hipError_t launch_collection_rows_gather(const uint64_t* sk, const uint32_t* lens, uint32_t s, uint32_t src0, uint32_t src1,
+                                         uint32_t dst0, uint32_t bounce_rows, const uint32_t* new_index, uint64_t* bounce,
+                                         uint32_t* bounce_lens, hipStream_t st);
+// pos[order[x]] = x, then out[p] = {pos[i], pos[j], common, total}
+hipError_t launch_collection_relabel(const uint32_t* order, uint32_t n, uint32_t* pos, const gg_pair* pairs, uint32_t cnt,
+                                     gg_pair* out, hipStream_t st);
+
 // synth.hip
 hipError_t launch_synth(uint32_t first_genome, uint32_t n_genomes, uint32_t genome_len,
                         uint32_t cluster_size, float max_sub_rate,

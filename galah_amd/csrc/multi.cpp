@@ -858,6 +858,40 @@ std::vector<uint32_t> balance_genomes(const gg_run* runs, uint64_t n_runs, uint3
 }
 
 }  // namespace
+
+gg_status sketch_files_first(gg_ctx* ctx, const char* const* paths, uint32_t n, const char* cache_dir,
+                             const uint64_t** d_sk, const uint32_t** d_len) {
+  const std::vector<gg_ctx*> ms = members(ctx);
+  gg_ctx* m = ms[0];
+  const uint32_t s = m->s;
+  std::vector<Rows> rows;
+  std::vector<RowSpan> spans;
+  std::vector<uint64_t> h_sk;
+  std::vector<uint32_t> h_len;
+  if (ms.size() > 1) {
+    h_sk.resize((size_t)std::max(n, 1u) * s);
+    h_len.resize(std::max(n, 1u));
+  }
+  const gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, ms.size() > 1 ? h_sk.data() : nullptr,
+                                            ms.size() > 1 ? h_len.data() : nullptr, nullptr);
+  if (st != GG_OK) return st;
+  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+  *d_sk = rows[0].sk;
+  *d_len = rows[0].len;
+  if (ms.size() > 1) {
+    uint64_t* up_sk;
+    uint32_t* up_len;
+    GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)std::max(n, 1u) * s, &up_sk));
+    GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)std::max(n, 1u), &up_len));
+    GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+    GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+    *d_sk = up_sk;
+    *d_len = up_len;
+  }
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  return GG_OK;
+}
+
 }  // namespace gg
 
 using namespace gg;

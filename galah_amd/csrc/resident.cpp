@@ -89,38 +89,6 @@ struct PairsForm {
   }
 };
 
-// The sized passes of a pair producer into scratch `key`: the first at `cap`,
-// one retry at the exact count.  run(d_out, cap, d_count) enqueues it on st.
-template <typename Run>
-gg_status sized_pair_passes(gg_ctx* c, const std::string& who, const char* key, uint64_t all, uint64_t cap,
-                            const Run& run, gg_pair** d_pairs, uint64_t* n_pairs, uint32_t* n_passes, hipStream_t st) {
-  gg_pair* d_out = nullptr;
-  uint64_t cnt = 0;
-  uint32_t passes = 0;
-  uint64_t *d_count, *h_count;
-  GG_HIP(c, scratch_t(c, "rs_count", 1, &d_count));
-  GG_HIP(c, host_scratch_t(c, "rs_count", 1, &h_count));
-  for (;;) {
-    if (passes == 2) return fail(c, GG_ERR_INTERNAL, who + ": pair output sizing failed");
-    GG_HIP(c, scratch_t(c, key, (size_t)std::max<uint64_t>(cap, 1), &d_out));
-    GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-    const gg_status ps = run(d_out, cap, d_count);
-    if (ps != GG_OK) return ps;
-    ++passes;
-    GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    GG_HIP(c, hipStreamSynchronize(st));
-    cnt = *h_count;
-    if (cnt > all) return fail(c, GG_ERR_INTERNAL, who + ": bad pair count");
-    if (cnt <= cap) break;
-    cap = cnt;
-  }
-  if (cnt >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, who + ": 2^31 pairs or more");
-  *d_pairs = d_out;
-  *n_pairs = cnt;
-  *n_passes = passes;
-  return GG_OK;
-}
-
 // The route of a call over resident rows by the context's pairs path.
 // DEFAULT: nothing is run.  MATRIX: the positions part, or GG_ERR_INVALID_ARG
 // when the limits fail.  AUTO: the positions part when the limits hold, and

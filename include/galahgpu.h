@@ -780,6 +780,100 @@ gg_status gg_precluster_files_resident(gg_ctx* ctx, const char* const* paths, ui
                                        const char* cache_dir, gg_pair** pairs, float** ani, uint64_t* n_out,
                                        gg_pairs_matrix_summary* summary);
 
+/* ---- a collection resident on the device ----------------- */
+/* The sketch matrix of a set of genomes, its passing pairs at one min_ani in
+ * (i, j) order and their f32 ANI, kept in device memory between calls:
+ * genomes are added to it, removed from it, and it is clustered in any genome
+ * order.  Only file bytes (or new rows) go up and rep_of comes down.
+ *
+ * Invariant after every successful call: the pair list equals
+ * gg_pairs(rows[0:n], min_ani) in content and order, and ani[p] ==
+ * gg_ani_f32(common, total, k) of pair p.
+ *
+ * A failed call leaves the collection as it was (a file that does not open
+ * or parse, a row index out of range, out of memory, GG_ERR_INVALID_ARG at the
+ * limits): new rows are written past n and n is raised last; a new pair list
+ * is built in the other of two buffers, which are swapped last.
+ *
+ * Limits: the border calls' (n < 2^31 genomes, fewer than 2^31 pairs); a call
+ * that would pass them is refused with GG_ERR_INVALID_ARG before anything is
+ * changed.
+ *
+ * The handle is owned by the caller and tied to the gg_ctx it was made on
+ * (destroy the collection first).  It acts on the context's first member, as
+ * the border calls do; a multi-device context sketches files on every member
+ * as gg_precluster_files_resident does and keeps the collection on the first
+ * (a collection is not sharded).  A collection is not thread-safe, and every
+ * call synchronises.  Its buffers are its own (never the context's scratch):
+ * device_bytes reports them. */
+typedef struct gg_collection gg_collection;
+typedef struct gg_collection_info {
+  uint64_t n_pairs;
+  uint64_t pair_capacity;
+  uint64_t device_bytes;
+  uint32_t n_rows;
+  uint32_t row_capacity;
+  uint32_t grows;       /* reallocations since create */
+  uint32_t rows_moved;  /* by the last gg_collection_remove */
+} gg_collection_info;
+
+/* An empty collection at min_ani (NaN is refused).  reserve_rows /
+ * reserve_pairs size the buffers at once; beyond them the capacity grows
+ * geometrically (allocate new, copy on the device, free old). */
+gg_status gg_collection_create(gg_ctx* ctx, float min_ani, uint32_t reserve_rows, uint64_t reserve_pairs,
+                               gg_collection** out);
+void gg_collection_destroy(gg_collection* collection);
+/* info and min_ani may each be NULL. */
+gg_status gg_collection_stat(const gg_collection* collection, gg_collection_info* info, float* min_ani);
+/* A collection from a state this library saved (gg_collection_rows and
+ * gg_collection_pairs, or the arrays of the border calls).  What the host
+ * forms check is checked: lens[g] <= sketch_size, i < j < n, the pairs
+ * strictly ascending by (i, j), no NaN ANI.  The pairs are NOT recomputed:
+ * the call trusts that they are gg_pairs(rows, min_ani) with their ANI. */
+gg_status gg_collection_load(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                             const gg_pair* pairs, const float* ani, uint64_t n_pairs, float min_ani,
+                             gg_collection** out);
+/* Adding genomes: the new rows take the indices n .. n + n_new - 1, and
+ * *n_border (may be NULL) receives the number of pairs added.  The border is
+ * routed by the context's pairs path exactly as gg_pairs_border_device routes
+ * it; gg_pair_paths, gg_pairs_paths_taken and gg_fallbacks count it like any
+ * border call.  It is sorted on the device and merged into the list without
+ * sorting the list again.  n_new == 0 is a no-op.
+ * _rows: host rows (lens[g] <= sketch_size is checked).  _rows_device: device
+ * rows, copied on `stream`, which the call synchronises (they must not be this
+ * collection's own arrays: growth frees those).  _files: paths are
+ * read and sketched as gg_sketch_files does (cache_dir and errors as there;
+ * GG_ERR_IO / GG_ERR_PARSE leave the collection unchanged), the hashes never
+ * visiting the host on a one-device context. */
+gg_status gg_collection_add_rows(gg_collection* collection, const uint64_t* sketches, const uint32_t* lens,
+                                 uint32_t n_new, uint64_t* n_border);
+gg_status gg_collection_add_rows_device(gg_collection* collection, const uint64_t* d_sketches, const uint32_t* d_lens,
+                                        uint32_t n_new, uint64_t* n_border, void* stream);
+gg_status gg_collection_add_files(gg_collection* collection, const char* const* paths, uint32_t n_new,
+                                  const char* cache_dir, uint64_t* n_border);
+/* Removing genomes: rows [m] in any order, repeats allowed (each row counts
+ * once); an index >= n is GG_ERR_INVALID_ARG.  The survivors keep their
+ * relative order; new_index (may be NULL) [n before the call] receives each
+ * row's new index, 0xFFFFFFFF for a removed row.  Removing nothing, or every
+ * row, is valid.  The pairs of the survivors are the old pairs with both ends
+ * kept, renumbered (no pair is evaluated); the rows are compacted in place,
+ * rows before the first removed one untouched (info.rows_moved). */
+gg_status gg_collection_remove(gg_collection* collection, const uint32_t* rows, uint32_t m, uint32_t* new_index);
+/* What gg_cluster_pairs(n, the pairs renumbered by position in `order`, ani,
+ * cluster_ani) returns: rep_of [n], positions in `order`.  order [n] maps
+ * position -> row (NULL: the identity) and must be a permutation (checked on
+ * the host, else GG_ERR_INVALID_ARG); a NaN threshold is refused. */
+gg_status gg_collection_cluster(gg_collection* collection, const uint32_t* order, float cluster_ani, uint32_t* rep_of);
+/* The pair list and its ANI, sorted by (i, j); gg_free both. */
+gg_status gg_collection_pairs(gg_collection* collection, gg_pair** pairs, float** ani, uint64_t* n_out);
+/* The rows: sketches [n x sketch_size], lens [n]. */
+gg_status gg_collection_rows(gg_collection* collection, uint64_t* sketches, uint32_t* lens);
+/* The device arrays themselves (each output may be NULL), valid until the next
+ * call that changes the collection: gg_preclusters_device, gg_ani_matrix_device
+ * and the like take them as they are. */
+gg_status gg_collection_view(gg_collection* collection, const uint64_t** d_sketches, const uint32_t** d_lens,
+                             const gg_pair** d_pairs, const float** d_ani);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);

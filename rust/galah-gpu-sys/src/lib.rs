@@ -202,6 +202,26 @@ pub struct gg_pairs_matrix_summary {
     pub pair_passes: u32,
 }
 
+/// Opaque collection resident on the device (`gg_collection`): owned by the
+/// caller, tied to the `gg_ctx` it was made on, not thread-safe.
+#[repr(C)]
+pub struct gg_collection {
+    _private: [u8; 0],
+}
+
+/// What `gg_collection_stat` reports (`gg_collection_info`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gg_collection_info {
+    pub n_pairs: u64,
+    pub pair_capacity: u64,
+    pub device_bytes: u64,
+    pub n_rows: u32,
+    pub row_capacity: u32,
+    pub grows: u32,
+    pub rows_moved: u32,
+}
+
 /// `gg_pair_sink`: a block of compared pairs; return 0 to go on.
 pub type gg_pair_sink = Option<unsafe extern "C" fn(user: *mut c_void, pairs: *const gg_pair, n: u64) -> c_int>;
 
@@ -402,6 +422,30 @@ extern "C" {
     pub fn gg_precluster_files_resident(ctx: *mut gg_ctx, paths: *const *const c_char, n_paths: u32, min_ani: f32,
                                         cache_dir: *const c_char, pairs: *mut *mut gg_pair, ani: *mut *mut f32,
                                         n_out: *mut u64, summary: *mut gg_pairs_matrix_summary) -> GgStatus;
+
+    // a collection resident on the device: add, remove and cluster genomes
+    pub fn gg_collection_create(ctx: *mut gg_ctx, min_ani: f32, reserve_rows: u32, reserve_pairs: u64,
+                                out: *mut *mut gg_collection) -> GgStatus;
+    pub fn gg_collection_destroy(collection: *mut gg_collection);
+    pub fn gg_collection_stat(collection: *const gg_collection, info: *mut gg_collection_info, min_ani: *mut f32)
+        -> GgStatus;
+    pub fn gg_collection_load(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, pairs: *const gg_pair,
+                              ani: *const f32, n_pairs: u64, min_ani: f32, out: *mut *mut gg_collection) -> GgStatus;
+    pub fn gg_collection_add_rows(collection: *mut gg_collection, sketches: *const u64, lens: *const u32, n_new: u32,
+                                  n_border: *mut u64) -> GgStatus;
+    pub fn gg_collection_add_rows_device(collection: *mut gg_collection, d_sketches: *const u64, d_lens: *const u32,
+                                         n_new: u32, n_border: *mut u64, stream: *mut c_void) -> GgStatus;
+    pub fn gg_collection_add_files(collection: *mut gg_collection, paths: *const *const c_char, n_new: u32,
+                                   cache_dir: *const c_char, n_border: *mut u64) -> GgStatus;
+    pub fn gg_collection_remove(collection: *mut gg_collection, rows: *const u32, m: u32, new_index: *mut u32)
+        -> GgStatus;
+    pub fn gg_collection_cluster(collection: *mut gg_collection, order: *const u32, cluster_ani: f32,
+                                 rep_of: *mut u32) -> GgStatus;
+    pub fn gg_collection_pairs(collection: *mut gg_collection, pairs: *mut *mut gg_pair, ani: *mut *mut f32,
+                               n_out: *mut u64) -> GgStatus;
+    pub fn gg_collection_rows(collection: *mut gg_collection, sketches: *mut u64, lens: *mut u32) -> GgStatus;
+    pub fn gg_collection_view(collection: *mut gg_collection, d_sketches: *mut *const u64, d_lens: *mut *const u32,
+                              d_pairs: *mut *const gg_pair, d_ani: *mut *const f32) -> GgStatus;
 
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;

@@ -51,28 +51,28 @@ INPUTS = {"c3_10k": (10000, 1000, (3e6, 3e6)), "c3_100k": (100000, 1000, (3e6, 3
 NEW_SHARES = {"border_1pct": 0.01, "border_10pct": 0.10}
 
 
-def synth_sketches(n, s, lengths, seed=5, device="cuda"):
-    """-> (d_sk [n, s] int64 holding the u64 hashes, ascending; d_lens [n] int32)."""
+def synth_sketches(n, s, lengths, seed=5, device="cuda", cluster=CLUSTER):
+    """-> (d_sk [n, s] int64 holding the u64 hashes, ascending; d_lens [n] int32); cluster: genomes per cluster."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
-    clusters = (n + CLUSTER - 1) // CLUSTER
+    clusters = (n + cluster - 1) // cluster
     lo, hi = lengths
     length = lo * (hi / lo) ** torch.rand(clusters, generator=g, device=device, dtype=torch.float64)
     bound = (2.0 * s / length * 2.0 ** 64).to(torch.int64)  # (below 2^63: 2 s < L / 2)
-    out = torch.empty((clusters * CLUSTER, s), dtype=torch.int64, device=device)
-    step = max(1, (1 << 24) // (CLUSTER * 2 * s))  # clusters per chunk: ~128 MB of candidates
+    out = torch.empty((clusters * cluster, s), dtype=torch.int64, device=device)
+    step = max(1, (1 << 24) // (cluster * 2 * s))  # clusters per chunk: ~128 MB of candidates
     for c0 in range(0, clusters, step):
         c1 = min(clusters, c0 + step)
         b = bound[c0:c1].to(torch.float64).view(-1, 1, 1)
         draw = lambda *shape: (torch.rand(*shape, generator=g, device=device, dtype=torch.float64) * b).to(torch.int64)
         base = draw(c1 - c0, 1, 2 * s)
-        rate = MAX_SUB * torch.rand((c1 - c0, CLUSTER, 1), generator=g, device=device, dtype=torch.float64)
-        keep = torch.rand((c1 - c0, CLUSTER, 2 * s), generator=g, device=device, dtype=torch.float64) < (1 - rate) ** K
-        member = torch.where(keep, base.expand(-1, CLUSTER, -1), draw(c1 - c0, CLUSTER, 2 * s))
+        rate = MAX_SUB * torch.rand((c1 - c0, cluster, 1), generator=g, device=device, dtype=torch.float64)
+        keep = torch.rand((c1 - c0, cluster, 2 * s), generator=g, device=device, dtype=torch.float64) < (1 - rate) ** K
+        member = torch.where(keep, base.expand(-1, cluster, -1), draw(c1 - c0, cluster, 2 * s))
         member = torch.sort(member, dim=2).values[:, :, :s]
-        out[c0 * CLUSTER:c1 * CLUSTER] = member.reshape(-1, s)
+        out[c0 * cluster:c1 * cluster] = member.reshape(-1, s)
     assert bool((out[:, 1:] > out[:, :-1]).all()), "a repeated hash in a synthetic sketch"
-    rows = torch.randperm(clusters * CLUSTER, generator=g, device=device)[:n]
+    rows = torch.randperm(clusters * cluster, generator=g, device=device)[:n]
     return out[rows].contiguous(), torch.full((n,), s, dtype=torch.int32, device=device)
 
 
