@@ -2,7 +2,9 @@
 gg_sketch_files with GALAHGPU_PARSE=device gives the same
 sketches as the host packer (GALAHGPU_PARSE=host) and as the oracle on the
 same files, across line layouts, record boundaries, byte classes, FASTQ,
-gzip, many files per batch, and the file errors.  Needs an MI355X."""
+gzip, many files per batch, and the file errors.  These sketches keep about
+one k-mer in fifty; test_device_parse_seams.py puts every chunk, wave, block,
+word and file seam under sketches that keep them all.  Needs an MI355X."""
 import gzip
 
 import numpy as np

@@ -4,7 +4,9 @@ packed_codes / place against a byte-by-byte restatement of pack.cpp's byte
 rules over 400k random 32-byte chunks (every block limit, line, header and
 base state at entry), and compress against its definition
 (tests/cpp/test_parse_core.cpp).  The device kernels themselves are checked
-end to end against the host packer in test_device_parse.py (GPU)."""
+end to end against the host packer in test_device_parse.py, and what joins
+the chunks -- chunk, wave, block, word and file seams -- on whole k-mer sets
+in test_device_parse_seams.py (GPU; its cases proved in test_parse_cases.py)."""
 import os
 import subprocess
 
