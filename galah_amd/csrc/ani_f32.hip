@@ -149,12 +149,9 @@ gg_status gg_ani_f32_device(gg_ctx* ctx, const gg_pair* d_pairs, uint64_t n_pair
     st = fail(m, GG_ERR_INVALID_ARG, "gg_ani_f32_device: d_pairs is not 16-byte aligned");
   else if (n_pairs >= (1ull << 31))
     st = fail(m, GG_ERR_INVALID_ARG, "gg_ani_f32_device: 2^31 pairs or more");
-  else if (hipSetDevice(m->device) != hipSuccess)
-    st = fail(m, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(m)) == GG_OK)
     st = ani_f32_device(m, d_pairs, n_pairs, d_ani, d_ani_f64, n_rechecked, (hipStream_t)stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, st);
 }
 
 }  // extern "C"

@@ -1080,11 +1080,12 @@ gg_status check_dense_input(const std::string& w, const uint64_t* sketches, cons
 template <class Run>
 gg_status dense_from_host(gg_ctx* pm, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
                           uint32_t count, size_t cells, uint32_t* common, uint32_t* total, float* ani, const Run& run) {
-  if (hipSetDevice(pm->device) != hipSuccess) return fail(pm, GG_ERR_HIP, "hipSetDevice failed");
+  gg_status st = use_device(pm);
+  if (st != GG_OK) return st;
   uint64_t* d_sk = nullptr;
   uint32_t *d_len = nullptr, *d_rows = nullptr, *d_common = nullptr, *d_total = nullptr;
   float* d_ani = nullptr;
-  gg_status st = upload_sketch_rows(pm, sketches, lens, n, rows, count, &d_sk, &d_len, &d_rows, pm->stream);
+  st = upload_sketch_rows(pm, sketches, lens, n, rows, count, &d_sk, &d_len, &d_rows, pm->stream);
   if (st != GG_OK) return st;
   if (common) GG_HIP(pm, scratch_t(pm, "mx_h_common", cells, &d_common));
   if (total) GG_HIP(pm, scratch_t(pm, "mx_h_total", cells, &d_total));
@@ -1190,9 +1191,7 @@ gg_status gg_ani_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const ui
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_device: no output asked for");
   else if (m && n && (!d_sketches || !d_lens))
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_device: null buffer");
-  else if (hipSetDevice(pm->device) != hipSuccess)
-    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(pm)) == GG_OK)
     st = ani_matrix_device(pm, d_sketches, d_lens, n, d_rows, m, d_common, d_total, d_ani, summary, (hipStream_t)stream);
   return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_matrix_summary{}; });
 }
@@ -1283,9 +1282,7 @@ gg_status gg_ani_matrix_groups_device(gg_ctx* ctx, const uint64_t* d_sketches, c
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_groups_device: no output asked for");
   else if (P && (!d_members || (n && (!d_sketches || !d_lens))))
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_matrix_groups_device: null buffer");
-  else if (hipSetDevice(pm->device) != hipSuccess)
-    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(pm)) == GG_OK)
     st = ani_matrix_groups_device(pm, d_sketches, d_lens, n, d_members, offsets, n_groups, d_common, d_total, d_ani,
                                   summary, (hipStream_t)stream);
   return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_matrix_summary{}; });

@@ -281,7 +281,8 @@ gg_status ani_pairs_ctx(gg_ctx* m, const uint64_t* sketches, const uint32_t* len
   if (st == GG_OK) st = check_list("gg_ani_pairs", n, list, cnt, err);
   if (st != GG_OK) return fail(m, st, err);
   if (cnt == 0) return GG_OK;
-  if (hipSetDevice(m->device) != hipSuccess) return fail(m, GG_ERR_HIP, "hipSetDevice failed");
+  st = use_device(m);
+  if (st != GG_OK) return st;
   uint64_t* d_sk = nullptr;
   uint32_t* d_len = nullptr;
   gg_pair* d_list = nullptr;
@@ -328,9 +329,7 @@ gg_status gg_ani_pairs(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* le
                        uint64_t m, float* ani) {
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* pm = primary(ctx);
-  const gg_status st = ani_pairs_ctx(pm, sketches, lens, n, list, m, ani);
-  if (st != GG_OK && pm != ctx) ctx->err = pm->err;
-  return st;
+  return finish_call(ctx, pm, ani_pairs_ctx(pm, sketches, lens, n, list, m, ani));
 }
 
 gg_status gg_ani_pairs_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
@@ -340,12 +339,9 @@ gg_status gg_ani_pairs_device(gg_ctx* ctx, const uint64_t* d_sketches, const uin
   gg_status st = GG_OK;
   if (m && (!d_list || (n && (!d_sketches || !d_lens))))
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_ani_pairs_device: null buffer");
-  else if (hipSetDevice(pm->device) != hipSuccess)
-    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(pm)) == GG_OK)
     st = ani_pairs_device(pm, d_sketches, d_lens, n, d_list, m, (hipStream_t)stream);
-  if (st != GG_OK && pm != ctx) ctx->err = pm->err;
-  return st;
+  return finish_call(ctx, pm, st);
 }
 
 gg_status gg_validate_clusters_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, uint32_t sketch_size,
@@ -400,10 +396,7 @@ gg_status gg_validate_clusters(gg_ctx* ctx, const uint64_t* sketches, const uint
   // members: the named list through the named-pair kernel (first member)
   std::vector<gg_pair> list = member_list_of(members, offsets, n_clusters);
   st = ani_pairs_ctx(pm, sketches, lens, n, list.data(), list.size(), nullptr);
-  if (st != GG_OK) {
-    if (pm != ctx) ctx->err = pm->err;
-    return st;
-  }
+  if (st != GG_OK) return finish_call(ctx, pm, st);
   // representatives: their rows gathered, through the all-pairs path at the
   // superset threshold (validate_core.hpp), then the f32 rule
   std::vector<gg_pair> reps;

@@ -1036,7 +1036,7 @@ gg_status pairs_tables(gg_ctx* c, float min_ani, uint32_t** d_cmin, uint32_t** d
 
 gg_status sorted_pairs_device(gg_ctx* c, const gg_pair* d_pairs, uint64_t cnt, uint32_t n, gg_pair** d_sorted,
                               hipStream_t st) {
-  // scratch as pairs_range_to_host lays it out: keys and sorted keys [cnt] u64,
+  // the sort's scratch, its one layout: keys and sorted keys [cnt] u64,
   // positions and sorted positions [cnt] u32, the sorted pairs [cnt] x 16 B
   uint64_t* d_kv;
   void* d_tmp;
@@ -1148,65 +1148,48 @@ gg_status pairs_range_to_host(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d
                               uint64_t tb, uint64_t te, float min_ani, std::vector<gg_pair>& res,
                               hipStream_t st, uint32_t n_old) {
   if (n < 2 || tb >= te) return GG_OK;
-  uint64_t *d_count, *h_count;
-  GG_HIP(c, scratch_t(c, "pair_count", 1, &d_count));
-  GG_HIP(c, host_scratch_t(c, "pair_count", 1, &h_count));
-  uint64_t cap = std::max<uint64_t>(1 << 20, (uint64_t)n * 16);
-  const uint64_t all = (uint64_t)n * (n > 0 ? n - 1 : 0) / 2;
-  cap = std::min<uint64_t>(cap, std::max<uint64_t>(all, 1));
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    gg_pair* d_out;
-    GG_HIP(c, scratch_t(c, "pair_out", cap, &d_out));
-    GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-    gg_status ps = pairs_core(c, d_sk, d_lens, n, tb, te, min_ani, d_out, cap, d_count, st, n_old);
-    if (ps != GG_OK) return ps;
-    GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  const uint64_t all = (uint64_t)n * (n - 1) / 2;
+  const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(1 << 20, (uint64_t)n * 16), all);
+  gg_pair* d_out = nullptr;
+  uint64_t cnt = 0;
+  uint32_t passes = 0;
+  gg_status r = sized_pair_passes(
+      c, "", "pair_out", all, cap,
+      [&](gg_pair* d_to, uint64_t pcap, uint64_t* d_count) {
+        return pairs_core(c, d_sk, d_lens, n, tb, te, min_ani, d_to, pcap, d_count, st, n_old);
+      },
+      &d_out, &cnt, &passes, st);
+  if (r != GG_OK) return r;
+  const size_t at = res.size();
+  res.resize(at + cnt);
+  if (cnt == 0) return GG_OK;
+  if (cnt < kDeviceSortPairs || cnt >= (1ull << 31)) {  // (few, or beyond the sort's int count: the host sorts)
+    GG_HIP(c, hipMemcpyAsync(res.data() + at, d_out, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
     GG_HIP(c, hipStreamSynchronize(st));
-    const uint64_t cnt = *h_count;
-    if (cnt <= cap) {
-      const size_t at = res.size();
-      res.resize(at + cnt);
-      if (cnt < kDeviceSortPairs || cnt >= (1ull << 31)) {  // (few, or beyond the sort's int count: the host sorts)
-        if (cnt) {
-          GG_HIP(c, hipMemcpyAsync(res.data() + at, d_out, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
-          GG_HIP(c, hipStreamSynchronize(st));
-          // in (i, j) order here, on the calling (member) thread: the members
-          // of a multi-device call sort their parts at the same time
-          std::sort(res.begin() + at, res.end(), [](const gg_pair& x, const gg_pair& y) {
-            return x.i != y.i ? x.i < y.i : x.j < y.j;
-          });
-        }
-        return GG_OK;
-      }
-      // many: sorted by (i, j) on the device and copied out in that order
-      // (scratch: keys and sorted keys [cnt] u64, positions and sorted
-      // positions [cnt] u32, the sorted pairs [cnt] x 16 B)
-      uint64_t* d_kv;
-      void* d_tmp;
-      const size_t tmp_bytes = pair_sort_tmp_bytes(cnt, n);
-      GG_HIP(c, scratch_t(c, "pair_sort_kv", 5 * cnt, &d_kv));
-      GG_HIP(c, scratch(c, "pair_sort_tmp", std::max<size_t>(tmp_bytes, 16), &d_tmp));
-      uint32_t* d_idx = (uint32_t*)(d_kv + 2 * cnt);
-      gg_pair* d_sorted = (gg_pair*)(d_kv + 3 * cnt);
-      GG_HIP(c, sort_pairs_device(d_out, cnt, n, d_kv, d_kv + cnt, d_idx, d_idx + cnt, d_sorted, d_tmp, tmp_bytes,
-                                  st));
-      // staged through a pinned chunk of at most kPairStage pairs (16 MiB), so
-      // a long-lived context holds no page-locked memory sized by its largest
-      // result
-      constexpr uint64_t kPairStage = 1ull << 20;
-      gg_pair* h_sorted;
-      GG_HIP(c, host_scratch_t(c, "pair_sorted", std::min(cnt, kPairStage), &h_sorted));
-      for (uint64_t x = 0; x < cnt; x += kPairStage) {
-        const uint64_t m = std::min(kPairStage, cnt - x);
-        GG_HIP(c, hipMemcpyAsync(h_sorted, d_sorted + x, m * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
-        GG_HIP(c, hipStreamSynchronize(st));
-        memcpy(res.data() + at + x, h_sorted, m * sizeof(gg_pair));
-      }
-      return GG_OK;
-    }
-    cap = cnt;
+    // in (i, j) order here, on the calling (member) thread: the members
+    // of a multi-device call sort their parts at the same time
+    std::sort(res.begin() + at, res.end(), [](const gg_pair& x, const gg_pair& y) {
+      return x.i != y.i ? x.i < y.i : x.j < y.j;
+    });
+    return GG_OK;
   }
-  return fail(c, GG_ERR_INTERNAL, "pair output sizing failed");
+  // many: sorted by (i, j) on the device and copied out in that order
+  gg_pair* d_sorted = nullptr;
+  r = sorted_pairs_device(c, d_out, cnt, n, &d_sorted, st);
+  if (r != GG_OK) return r;
+  // staged through a pinned chunk of at most kPairStage pairs (16 MiB), so
+  // a long-lived context holds no page-locked memory sized by its largest
+  // result
+  constexpr uint64_t kPairStage = 1ull << 20;
+  gg_pair* h_sorted;
+  GG_HIP(c, host_scratch_t(c, "pair_sorted", std::min(cnt, kPairStage), &h_sorted));
+  for (uint64_t x = 0; x < cnt; x += kPairStage) {
+    const uint64_t m = std::min(kPairStage, cnt - x);
+    GG_HIP(c, hipMemcpyAsync(h_sorted, d_sorted + x, m * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
+    GG_HIP(c, hipStreamSynchronize(st));
+    memcpy(res.data() + at + x, h_sorted, m * sizeof(gg_pair));
+  }
+  return GG_OK;
 }
 
 double ani_f64(uint32_t common, uint32_t total, int k) {
@@ -1397,24 +1380,17 @@ int gg_device(const gg_ctx* ctx) {
   return ctx->devs.empty() ? ctx->device : ctx->devs[0]->device;
 }
 
-static gg_status gg_sketch_device_one(gg_ctx* ctx, const uint32_t* d_words, uint64_t n_words,
-                           const gg_run* runs, uint64_t n_runs, uint32_t n_genomes,
-                           uint64_t* d_out, uint32_t* d_lens, void* stream) {
-  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
-  if ((n_runs && (!runs || !d_words)) || (n_genomes && (!d_out || !d_lens)))
-    return fail(ctx, GG_ERR_INVALID_ARG, "gg_sketch_device: null buffer");
-  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;  // NULL = the default stream
-  return sketch_core(ctx, d_words, n_words, runs, n_runs, n_genomes, d_out, d_lens, nullptr, st);
-}
-
 gg_status gg_sketch_device(gg_ctx* ctx, const uint32_t* d_words, uint64_t n_words,
                            const gg_run* runs, uint64_t n_runs, uint32_t n_genomes,
                            uint64_t* d_out, uint32_t* d_lens, void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* m = primary(ctx);
-  const gg_status st = gg_sketch_device_one(m, d_words, n_words, runs, n_runs, n_genomes, d_out, d_lens, stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  gg_status st;
+  if ((n_runs && (!runs || !d_words)) || (n_genomes && (!d_out || !d_lens)))
+    st = fail(m, GG_ERR_INVALID_ARG, "gg_sketch_device: null buffer");
+  else if ((st = use_device(m)) == GG_OK)  // (stream NULL = the default stream)
+    st = sketch_core(m, d_words, n_words, runs, n_runs, n_genomes, d_out, d_lens, nullptr, (hipStream_t)stream);
+  return finish_call(ctx, m, st);
 }
 
 uint64_t gg_pair_tiles(uint32_t n) {
@@ -1452,26 +1428,19 @@ void gg_pair_partition(uint32_t n, uint32_t parts, uint32_t part, uint64_t* begi
   if (*end < *begin) *end = *begin;
 }
 
-static gg_status gg_pairs_device_one(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens,
-                          uint32_t n, uint64_t tile_begin, uint64_t tile_end, float min_ani,
-                          gg_pair* d_out, uint64_t out_cap, uint64_t* d_count, void* stream) {
-  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
-  if (n && (!d_sketches || !d_lens || !d_count || (out_cap && !d_out)))
-    return fail(ctx, GG_ERR_INVALID_ARG, "gg_pairs_device: null buffer");
-  if (std::isnan(min_ani)) return fail(ctx, GG_ERR_INVALID_ARG, "min_ani is NaN");
-  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  hipStream_t st = (hipStream_t)stream;  // NULL = the default stream
-  return pairs_core(ctx, d_sketches, d_lens, n, tile_begin, tile_end, min_ani, d_out, out_cap,
-                    d_count, st);
-}
-
 gg_status gg_pairs_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens,
                           uint32_t n, uint64_t tile_begin, uint64_t tile_end, float min_ani,
                           gg_pair* d_out, uint64_t out_cap, uint64_t* d_count, void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* m = primary(ctx);
-  const gg_status st = gg_pairs_device_one(m, d_sketches, d_lens, n, tile_begin, tile_end, min_ani, d_out, out_cap, d_count, stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  gg_status st;
+  if (n && (!d_sketches || !d_lens || !d_count || (out_cap && !d_out)))
+    st = fail(m, GG_ERR_INVALID_ARG, "gg_pairs_device: null buffer");
+  else if (std::isnan(min_ani))
+    st = fail(m, GG_ERR_INVALID_ARG, "min_ani is NaN");
+  else if ((st = use_device(m)) == GG_OK)  // (stream NULL = the default stream)
+    st = pairs_core(m, d_sketches, d_lens, n, tile_begin, tile_end, min_ani, d_out, out_cap, d_count, (hipStream_t)stream);
+  return finish_call(ctx, m, st);
 }
 
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length) {
@@ -1657,13 +1626,14 @@ gg_status gg_timing_read(gg_ctx* ctx, int kernel, gg_kernel_stats* out) {
   return GG_OK;
 }
 
-static gg_status gg_synth_clustered_device_one(gg_ctx* ctx, uint32_t first_genome, uint32_t n_genomes, uint32_t genome_len,
-                                    uint32_t cluster_size, float max_sub_rate, uint64_t seed,
-                                    uint32_t* d_words, gg_run* runs, void* stream) {
-  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+// gg_synth_clustered_device behind its context lookup
+static gg_status synth_clustered_ctx(gg_ctx* ctx, uint32_t first_genome, uint32_t n_genomes, uint32_t genome_len,
+                                     uint32_t cluster_size, float max_sub_rate, uint64_t seed, uint32_t* d_words,
+                                     gg_run* runs, void* stream) {
   if (!d_words || !runs || genome_len % 16 || genome_len < (uint32_t)ctx->k || cluster_size == 0)
     return fail(ctx, GG_ERR_INVALID_ARG, "gg_synth_clustered_device: bad arguments");
-  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+  const gg_status ds = use_device(ctx);
+  if (ds != GG_OK) return ds;
   hipStream_t st = (hipStream_t)stream;  // NULL = the default stream
   GG_HIP(ctx, launch_synth(first_genome, n_genomes, genome_len, cluster_size, max_sub_rate, seed, d_words, st));
   for (uint32_t g = 0; g < n_genomes; ++g) runs[g] = gg_run{g, genome_len, (uint64_t)g * genome_len};
@@ -1673,10 +1643,10 @@ static gg_status gg_synth_clustered_device_one(gg_ctx* ctx, uint32_t first_genom
 gg_status gg_synth_clustered_device(gg_ctx* ctx, uint32_t first_genome, uint32_t n_genomes, uint32_t genome_len,
                                     uint32_t cluster_size, float max_sub_rate, uint64_t seed,
                                     uint32_t* d_words, gg_run* runs, void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* m = primary(ctx);
-  const gg_status st = gg_synth_clustered_device_one(m, first_genome, n_genomes, genome_len, cluster_size, max_sub_rate, seed, d_words, runs, stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, synth_clustered_ctx(m, first_genome, n_genomes, genome_len, cluster_size, max_sub_rate, seed,
+                                                 d_words, runs, stream));
 }
 
 static uint64_t splitmix_host(uint64_t x) {
@@ -1700,15 +1670,16 @@ gg_status gg_synth_mixed_lengths(uint32_t first_genome, uint32_t n_genomes, uint
   return GG_OK;
 }
 
-static gg_status gg_synth_mixed_device_one(gg_ctx* ctx, uint32_t first_genome, uint32_t n_genomes, const uint32_t* lens,
-                                uint32_t cluster_size, float max_sub_rate, double n_run_rate, uint64_t seed,
-                                uint32_t* d_words, gg_run* runs, uint64_t runs_cap, uint64_t* n_runs, void* stream) {
-  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
+// gg_synth_mixed_device behind its context lookup
+static gg_status synth_mixed_ctx(gg_ctx* ctx, uint32_t first_genome, uint32_t n_genomes, const uint32_t* lens,
+                                 uint32_t cluster_size, float max_sub_rate, double n_run_rate, uint64_t seed,
+                                 uint32_t* d_words, gg_run* runs, uint64_t runs_cap, uint64_t* n_runs, void* stream) {
   if (!d_words || !lens || !n_runs || cluster_size == 0 || !(n_run_rate >= 0.0 && n_run_rate < 1.0))
     return fail(ctx, GG_ERR_INVALID_ARG, "gg_synth_mixed_device: bad arguments");
   for (uint32_t g = 0; g < n_genomes; ++g)
     if (lens[g] % 16 || lens[g] == 0) return fail(ctx, GG_ERR_INVALID_ARG, "genome lengths must be positive multiples of 16");
-  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+  const gg_status ds = use_device(ctx);
+  if (ds != GG_OK) return ds;
   hipStream_t st = (hipStream_t)stream;
   std::vector<uint64_t> woff(n_genomes + 1, 0);
   uint64_t max_words = 0;
@@ -1750,10 +1721,10 @@ static gg_status gg_synth_mixed_device_one(gg_ctx* ctx, uint32_t first_genome, u
 gg_status gg_synth_mixed_device(gg_ctx* ctx, uint32_t first_genome, uint32_t n_genomes, const uint32_t* lens,
                                 uint32_t cluster_size, float max_sub_rate, double n_run_rate, uint64_t seed,
                                 uint32_t* d_words, gg_run* runs, uint64_t runs_cap, uint64_t* n_runs, void* stream) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* m = primary(ctx);
-  const gg_status st = gg_synth_mixed_device_one(m, first_genome, n_genomes, lens, cluster_size, max_sub_rate, n_run_rate, seed, d_words, runs, runs_cap, n_runs, stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, synth_mixed_ctx(m, first_genome, n_genomes, lens, cluster_size, max_sub_rate, n_run_rate, seed,
+                                             d_words, runs, runs_cap, n_runs, stream));
 }
 
 }  // extern "C"

@@ -52,7 +52,8 @@ gg_status pairs_border_ctx(gg_ctx* m, const uint64_t* sketches, const uint32_t* 
   for (uint32_t i = 0; i < n; ++i)
     if (lens[i] > m->s) return fail(m, GG_ERR_INVALID_ARG, "sketch longer than sketch_size");
   if (n < 2 || n_old >= n) return GG_OK;
-  if (hipSetDevice(m->device) != hipSuccess) return fail(m, GG_ERR_HIP, "hipSetDevice failed");
+  const gg_status ds = use_device(m);
+  if (ds != GG_OK) return ds;
   uint64_t* d_sk = nullptr;
   uint32_t* d_len = nullptr;
   GG_HIP(m, scratch_t(m, "bd_sk", (size_t)n * m->s, &d_sk));
@@ -72,7 +73,8 @@ gg_status update_files_ctx(gg_ctx* m, const uint64_t* old_sketches, const uint32
   gg_status st = gg_sketch_files(m, new_paths, n_new, cache_dir, new_hashes, new_lens, nullptr);
   if (st != GG_OK) return st;
   const uint32_t n = n_old + n_new;
-  if (hipSetDevice(m->device) != hipSuccess) return fail(m, GG_ERR_HIP, "hipSetDevice failed");
+  st = use_device(m);
+  if (st != GG_OK) return st;
   uint64_t* d_sk = nullptr;
   uint32_t* d_len = nullptr;
   GG_HIP(m, scratch_t(m, "bd_sk", (size_t)n * m->s, &d_sk));
@@ -141,14 +143,9 @@ gg_status gg_pairs_border(gg_ctx* ctx, const uint64_t* sketches, const uint32_t*
   gg_ctx* m = primary(ctx);
   std::vector<gg_pair> res;
   st = pairs_border_ctx(m, sketches, lens, n, n_old, min_ani, res);
-  if (st != GG_OK) {
-    if (m != ctx) ctx->err = m->err;
-    return st;
-  }
-  *out = copy_out(res);
-  if (!*out) return fail(ctx, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-  *n_out = res.size();
-  return GG_OK;
+  if (st == GG_OK && !(*out = copy_out(res))) st = fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+  if (st == GG_OK) *n_out = res.size();
+  return finish_call(ctx, m, st);
 }
 
 gg_status gg_pairs_border_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
@@ -161,16 +158,16 @@ gg_status gg_pairs_border_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
   if (n_old > n) return fail(ctx, GG_ERR_INVALID_ARG, "gg_pairs_border_device: n_old exceeds n");
   if (n < 2 || n_old == n) return GG_OK;
   gg_ctx* m = primary(ctx);
-  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
   bool matrix = false;
-  gg_status st = border_routed_append(m, "gg_pairs_border_device", d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap,
-                                      d_count, &matrix, (hipStream_t)stream);
+  gg_status st = use_device(m);
+  if (st == GG_OK)
+    st = border_routed_append(m, "gg_pairs_border_device", d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count,
+                              &matrix, (hipStream_t)stream);
   if (st == GG_OK && !matrix)
     st = pairs_core(m, d_sketches, d_lens, n, 0, gg_pair_tiles(n), min_ani, d_out, out_cap, d_count, (hipStream_t)stream,
                     n_old);
   if (st == GG_OK) count_pairs_path(m, matrix);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, st);
 }
 
 gg_status gg_update_files(gg_ctx* ctx, const uint64_t* old_sketches, const uint32_t* old_lens, uint32_t n_old,
@@ -187,24 +184,18 @@ gg_status gg_update_files(gg_ctx* ctx, const uint64_t* old_sketches, const uint3
   *n_out = 0;
   gg_ctx* m = primary(ctx);
   std::vector<gg_pair> res;
-  const gg_status st =
+  gg_status st =
       update_files_ctx(m, old_sketches, old_lens, n_old, new_paths, n_new, min_ani, cache_dir, new_hashes, new_lens, res);
-  if (st != GG_OK) {
-    if (m != ctx) ctx->err = m->err;
-    return st;
+  if (st == GG_OK) {
+    *pairs = copy_out(res);
+    *ani = (float*)malloc(std::max<size_t>(res.size(), 1) * sizeof(float));
+    if (!*pairs || !*ani) st = fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
   }
-  *pairs = copy_out(res);
-  *ani = (float*)malloc(std::max<size_t>(res.size(), 1) * sizeof(float));
-  if (!*pairs || !*ani) {
-    free(*pairs);
-    free(*ani);
-    *pairs = nullptr;
-    *ani = nullptr;
-    return fail(ctx, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+  if (st == GG_OK) {
+    for (size_t p = 0; p < res.size(); ++p) (*ani)[p] = gg_ani_f32(res[p].common, res[p].total, m->k);  // src/finch.rs:70
+    *n_out = res.size();
   }
-  for (size_t p = 0; p < res.size(); ++p) (*ani)[p] = gg_ani_f32(res[p].common, res[p].total, m->k);  // src/finch.rs:70
-  *n_out = res.size();
-  return GG_OK;
+  return finish_call(ctx, m, st, [&] { free_out(pairs, ani); });
 }
 
 }  // extern "C"

@@ -320,43 +320,42 @@ gg_status gg_cluster_pairs_device(gg_ctx* ctx, uint32_t n_genomes, const gg_pair
     st = fail(m, GG_ERR_INVALID_ARG, "gg_cluster_pairs_device: cluster_ani is NaN");
   else if (n_pairs >= (1ull << 31) || n_genomes >= (1u << 31))
     st = fail(m, GG_ERR_INVALID_ARG, "gg_cluster_pairs_device: 2^31 pairs or genomes, or more");
-  else if (hipSetDevice(m->device) != hipSuccess)
-    st = fail(m, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(m)) == GG_OK)
     st = cluster_device(m, n_genomes, d_pairs, d_ani, n_pairs, cluster_ani, d_rep_of, (hipStream_t)stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, st);
+}
+
+// gg_cluster_pairs behind its context lookup
+static gg_status cluster_pairs_ctx(gg_ctx* m, uint32_t n_genomes, const gg_pair* pairs, const float* ani, uint64_t n_pairs,
+                                   float cluster_ani, uint32_t* rep_of) {
+  const gg_status chk = cluster_check_input("gg_cluster_pairs", n_genomes, pairs, ani, n_pairs, cluster_ani, rep_of);
+  if (chk != GG_OK) return fail(m, chk, gg_thread_last_error());
+  if (n_genomes >= (1u << 31)) return fail(m, GG_ERR_INVALID_ARG, "gg_cluster_pairs: 2^31 genomes or more");
+  if (n_genomes == 0) return GG_OK;
+  gg_status st = use_device(m);
+  if (st != GG_OK) return st;
+  gg_pair* d_pairs = nullptr;
+  float* d_ani = nullptr;
+  uint32_t* d_rep = nullptr;
+  GG_HIP(m, scratch_t(m, "cl_in_pairs", (size_t)n_pairs, &d_pairs));
+  GG_HIP(m, scratch_t(m, "cl_in_ani", (size_t)n_pairs, &d_ani));
+  GG_HIP(m, scratch_t(m, "cl_rep", (size_t)n_genomes, &d_rep));
+  if (n_pairs) {
+    GG_HIP(m, hipMemcpyAsync(d_pairs, pairs, n_pairs * sizeof(gg_pair), hipMemcpyHostToDevice, m->stream));
+    GG_HIP(m, hipMemcpyAsync(d_ani, ani, n_pairs * sizeof(float), hipMemcpyHostToDevice, m->stream));
+  }
+  st = cluster_device(m, n_genomes, d_pairs, d_ani, n_pairs, cluster_ani, d_rep, m->stream);
+  if (st != GG_OK) return st;
+  GG_HIP(m, hipMemcpyAsync(rep_of, d_rep, (size_t)n_genomes * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  return GG_OK;
 }
 
 gg_status gg_cluster_pairs(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* pairs, const float* ani, uint64_t n_pairs,
                            float cluster_ani, uint32_t* rep_of) {
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* m = primary(ctx);
-  auto run = [&]() -> gg_status {
-    const gg_status chk = cluster_check_input("gg_cluster_pairs", n_genomes, pairs, ani, n_pairs, cluster_ani, rep_of);
-    if (chk != GG_OK) return fail(m, chk, gg_thread_last_error());
-    if (n_genomes >= (1u << 31)) return fail(m, GG_ERR_INVALID_ARG, "gg_cluster_pairs: 2^31 genomes or more");
-    if (n_genomes == 0) return GG_OK;
-    if (hipSetDevice(m->device) != hipSuccess) return fail(m, GG_ERR_HIP, "hipSetDevice failed");
-    gg_pair* d_pairs = nullptr;
-    float* d_ani = nullptr;
-    uint32_t* d_rep = nullptr;
-    GG_HIP(m, scratch_t(m, "cl_in_pairs", (size_t)n_pairs, &d_pairs));
-    GG_HIP(m, scratch_t(m, "cl_in_ani", (size_t)n_pairs, &d_ani));
-    GG_HIP(m, scratch_t(m, "cl_rep", (size_t)n_genomes, &d_rep));
-    if (n_pairs) {
-      GG_HIP(m, hipMemcpyAsync(d_pairs, pairs, n_pairs * sizeof(gg_pair), hipMemcpyHostToDevice, m->stream));
-      GG_HIP(m, hipMemcpyAsync(d_ani, ani, n_pairs * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    }
-    const gg_status st = cluster_device(m, n_genomes, d_pairs, d_ani, n_pairs, cluster_ani, d_rep, m->stream);
-    if (st != GG_OK) return st;
-    GG_HIP(m, hipMemcpyAsync(rep_of, d_rep, (size_t)n_genomes * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    GG_HIP(m, hipStreamSynchronize(m->stream));
-    return GG_OK;
-  };
-  const gg_status st = run();
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, cluster_pairs_ctx(m, n_genomes, pairs, ani, n_pairs, cluster_ani, rep_of));
 }
 
 gg_status gg_cluster_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani, float cluster_ani,

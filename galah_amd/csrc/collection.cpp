@@ -45,15 +45,7 @@ constexpr uint64_t kBounceBytes = 64ull << 20;
 gg_ctx* first(gg_collection* c) { return primary(c->ctx); }
 
 // the tail of every entry point: the message of a failure goes to the context given
-gg_status finish(gg_collection* c, gg_status st) {
-  gg_ctx* m = first(c);
-  if (st != GG_OK && m != c->ctx) c->ctx->err = m->err;
-  return st;
-}
-
-gg_status use_device(gg_ctx* m) {
-  return hipSetDevice(m->device) == hipSuccess ? GG_OK : fail(m, GG_ERR_HIP, "hipSetDevice failed");
-}
+gg_status finish(gg_collection* c, gg_status st) { return finish_call(c->ctx, first(c), st); }
 
 // the rows' capacity raised to hold `need`: allocate new, copy, free old
 gg_status reserve_rows(gg_collection* c, uint64_t need, hipStream_t st) {
@@ -172,6 +164,7 @@ gg_status add_rows_device(gg_collection* c, const char* who, const uint64_t* d_s
         },
         &d_border, &cnt, &passes, st);
     if (r != GG_OK) return r;
+    if (cnt >= (1ull << 31)) return fail(m, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 pairs or more");
     count_pairs_path(m, matrix);
     if (c->n_pairs + cnt >= (1ull << 31)) return fail(m, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 pairs or more");
     if (cnt) {
@@ -317,6 +310,65 @@ gg_status cluster_rows(gg_collection* c, const uint32_t* order, float cluster_an
   return GG_OK;
 }
 
+// host rows (checked) into context scratch, then add_rows_device
+gg_status add_rows_host(gg_collection* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n_new,
+                        uint64_t* n_border) {
+  gg_ctx* m = first(c);
+  if (!sketches || !lens) return fail(m, GG_ERR_INVALID_ARG, "gg_collection_add_rows: null buffer");
+  for (uint32_t g = 0; g < n_new; ++g)
+    if (lens[g] > m->s) return fail(m, GG_ERR_INVALID_ARG, "gg_collection_add_rows: sketch longer than sketch_size");
+  gg_status st = use_device(m);
+  if (st != GG_OK) return st;
+  uint64_t* d_sk;
+  uint32_t* d_len;
+  GG_HIP(m, scratch_t(m, "co_up_sk", (size_t)n_new * m->s, &d_sk));
+  GG_HIP(m, scratch_t(m, "co_up_len", (size_t)n_new, &d_len));
+  GG_HIP(m, hipMemcpyAsync(d_sk, sketches, (size_t)n_new * m->s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+  GG_HIP(m, hipMemcpyAsync(d_len, lens, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+  return add_rows_device(c, "gg_collection_add_rows", d_sk, d_len, n_new, n_border, m->stream);
+}
+
+// a saved state into the buffers of a collection just created for it
+gg_status load_state(gg_collection* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const gg_pair* pairs,
+                     const float* ani, uint64_t n_pairs) {
+  gg_ctx* m = first(c);
+  hipStream_t s = m->stream;
+  if (n) {
+    GG_HIP(m, hipMemcpyAsync(c->sk, sketches, (size_t)n * m->s * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    GG_HIP(m, hipMemcpyAsync(c->lens, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  }
+  if (n_pairs) {
+    GG_HIP(m, hipMemcpyAsync(c->pairs[0], pairs, (size_t)n_pairs * sizeof(gg_pair), hipMemcpyHostToDevice, s));
+    GG_HIP(m, hipMemcpyAsync(c->ani[0], ani, (size_t)n_pairs * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+  GG_HIP(m, hipStreamSynchronize(s));
+  c->n = n;
+  c->n_pairs = n_pairs;
+  return GG_OK;
+}
+
+gg_status pairs_to_host(gg_collection* c, gg_pair** pairs, float** ani, uint64_t* n_out) {
+  gg_ctx* m = first(c);
+  gg_status st = use_device(m);
+  if (st == GG_OK) st = copy_out(m, c->pairs[c->cur], c->n_pairs, pairs, m->stream);
+  if (st == GG_OK) st = copy_out(m, c->ani[c->cur], c->n_pairs, ani, m->stream);
+  if (st != GG_OK) return st;
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  *n_out = c->n_pairs;
+  return GG_OK;
+}
+
+gg_status rows_to_host(gg_collection* c, uint64_t* sketches, uint32_t* lens) {
+  gg_ctx* m = first(c);
+  if (!sketches || !lens) return fail(m, GG_ERR_INVALID_ARG, "gg_collection_rows: null argument");
+  const gg_status st = use_device(m);
+  if (st != GG_OK) return st;
+  GG_HIP(m, hipMemcpyAsync(sketches, c->sk, (size_t)c->n * m->s * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipMemcpyAsync(lens, c->lens, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  return GG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -326,10 +378,7 @@ gg_status gg_collection_create(gg_ctx* ctx, float min_ani, uint32_t reserve_rows
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   if (!out) return fail(ctx, GG_ERR_INVALID_ARG, "gg_collection_create: null argument");
   *out = nullptr;
-  gg_ctx* m = primary(ctx);
-  const gg_status st = create(ctx, min_ani, reserve_rows_, reserve_pairs_, out);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, primary(ctx), create(ctx, min_ani, reserve_rows_, reserve_pairs_, out));
 }
 
 void gg_collection_destroy(gg_collection* c) { release(c); }
@@ -371,31 +420,9 @@ gg_status gg_collection_load(gg_ctx* ctx, const uint64_t* sketches, const uint32
   }
   gg_collection* c = nullptr;
   gg_status st = create(ctx, min_ani, n, n_pairs, &c);
-  if (st == GG_OK) {
-    auto up = [&]() -> gg_status {
-      hipStream_t s = m->stream;
-      if (n) {
-        GG_HIP(m, hipMemcpyAsync(c->sk, sketches, (size_t)n * m->s * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        GG_HIP(m, hipMemcpyAsync(c->lens, lens, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-      }
-      if (n_pairs) {
-        GG_HIP(m, hipMemcpyAsync(c->pairs[0], pairs, (size_t)n_pairs * sizeof(gg_pair), hipMemcpyHostToDevice, s));
-        GG_HIP(m, hipMemcpyAsync(c->ani[0], ani, (size_t)n_pairs * sizeof(float), hipMemcpyHostToDevice, s));
-      }
-      GG_HIP(m, hipStreamSynchronize(s));
-      return GG_OK;
-    };
-    st = up();
-    if (st == GG_OK) {
-      c->n = n;
-      c->n_pairs = n_pairs;
-      *out = c;
-    } else {
-      release(c);
-    }
-  }
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  if (st == GG_OK) st = load_state(c, sketches, lens, n, pairs, ani, n_pairs);
+  if (st == GG_OK) *out = c;
+  return finish_call(ctx, m, st, [&] { release(c); });
 }
 
 gg_status gg_collection_add_rows_device(gg_collection* c, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n_new,
@@ -415,22 +442,7 @@ gg_status gg_collection_add_rows(gg_collection* c, const uint64_t* sketches, con
   if (!c) return fail(nullptr, GG_ERR_INVALID_ARG, "null collection");
   if (n_border) *n_border = 0;
   if (n_new == 0) return GG_OK;
-  gg_ctx* m = first(c);
-  auto run = [&]() -> gg_status {
-    if (!sketches || !lens) return fail(m, GG_ERR_INVALID_ARG, "gg_collection_add_rows: null buffer");
-    for (uint32_t g = 0; g < n_new; ++g)
-      if (lens[g] > m->s) return fail(m, GG_ERR_INVALID_ARG, "gg_collection_add_rows: sketch longer than sketch_size");
-    gg_status st = use_device(m);
-    if (st != GG_OK) return st;
-    uint64_t* d_sk;
-    uint32_t* d_len;
-    GG_HIP(m, scratch_t(m, "co_up_sk", (size_t)n_new * m->s, &d_sk));
-    GG_HIP(m, scratch_t(m, "co_up_len", (size_t)n_new, &d_len));
-    GG_HIP(m, hipMemcpyAsync(d_sk, sketches, (size_t)n_new * m->s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-    GG_HIP(m, hipMemcpyAsync(d_len, lens, (size_t)n_new * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-    return add_rows_device(c, "gg_collection_add_rows", d_sk, d_len, n_new, n_border, m->stream);
-  };
-  return finish(c, run());
+  return finish(c, add_rows_host(c, sketches, lens, n_new, n_border));
 }
 
 gg_status gg_collection_add_files(gg_collection* c, const char* const* paths, uint32_t n_new, const char* cache_dir,
@@ -446,11 +458,8 @@ gg_status gg_collection_add_files(gg_collection* c, const char* const* paths, ui
   // device and copied from there into the matrix
   const uint64_t* d_sk = nullptr;
   const uint32_t* d_len = nullptr;
-  gg_status st = sketch_files_first(c->ctx, paths, n_new, cache_dir, &d_sk, &d_len);
-  if (st != GG_OK) {
-    if (m != c->ctx && !c->ctx->err.empty()) m->err = c->ctx->err;  // (the sketch step reports on the context given)
-    return finish(c, st);
-  }
+  const gg_status st = sketch_files_first(c->ctx, paths, n_new, cache_dir, &d_sk, &d_len);
+  if (st != GG_OK) return st;  // (reported on the context given)
   return finish(c, add_rows_device(c, "gg_collection_add_files", d_sk, d_len, n_new, n_border, m->stream));
 }
 
@@ -472,45 +481,15 @@ gg_status gg_collection_pairs(gg_collection* c, gg_pair** pairs, float** ani, ui
   *pairs = nullptr;
   *ani = nullptr;
   *n_out = 0;
-  auto run = [&]() -> gg_status {
-    gg_status st = use_device(m);
-    if (st != GG_OK) return st;
-    const uint64_t cnt = c->n_pairs;
-    *pairs = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
-    *ani = (float*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(float));
-    if (!*pairs || !*ani) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-    if (cnt) {
-      GG_HIP(m, hipMemcpyAsync(*pairs, c->pairs[c->cur], cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, m->stream));
-      GG_HIP(m, hipMemcpyAsync(*ani, c->ani[c->cur], cnt * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    }
-    GG_HIP(m, hipStreamSynchronize(m->stream));
-    *n_out = cnt;
-    return GG_OK;
-  };
-  const gg_status st = run();
-  if (st != GG_OK) {
-    free(*pairs);
-    free(*ani);
-    *pairs = nullptr;
-    *ani = nullptr;
-  }
+  const gg_status st = pairs_to_host(c, pairs, ani, n_out);
+  if (st != GG_OK) free_out(pairs, ani);
   return finish(c, st);
 }
 
 gg_status gg_collection_rows(gg_collection* c, uint64_t* sketches, uint32_t* lens) {
   if (!c) return fail(nullptr, GG_ERR_INVALID_ARG, "null collection");
-  gg_ctx* m = first(c);
   if (c->n == 0) return GG_OK;
-  auto run = [&]() -> gg_status {
-    if (!sketches || !lens) return fail(m, GG_ERR_INVALID_ARG, "gg_collection_rows: null argument");
-    gg_status st = use_device(m);
-    if (st != GG_OK) return st;
-    GG_HIP(m, hipMemcpyAsync(sketches, c->sk, (size_t)c->n * m->s * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
-    GG_HIP(m, hipMemcpyAsync(lens, c->lens, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    GG_HIP(m, hipStreamSynchronize(m->stream));
-    return GG_OK;
-  };
-  return finish(c, run());
+  return finish(c, rows_to_host(c, sketches, lens));
 }
 
 gg_status gg_collection_view(gg_collection* c, const uint64_t** d_sketches, const uint32_t** d_lens, const gg_pair** d_pairs,

@@ -328,8 +328,16 @@ gg_status check_sketch_rows(const std::string& w, const uint32_t* lens, uint32_t
                             const uint32_t* rows, uint32_t count, bool listed_once, std::string& err);
 gg_status upload_sketch_rows(gg_ctx* c, const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint32_t* rows,
                              uint32_t count, uint64_t** d_sk, uint32_t** d_len, uint32_t** d_rows, hipStream_t st);
-// The tail of an extern "C" entry point that ran on pm = primary(ctx): on
-// failure on_failure() puts the outputs back and the message goes to ctx.
+// The host call frame of an extern "C" entry point that runs on pm =
+// primary(ctx): use_device(pm) before its first HIP call, every failure
+// reported on pm (fail, GG_HIP), and finish_call as its last statement: on
+// failure on_failure() puts the outputs back -- the entry point's one cleanup
+// -- and the message goes to ctx.  (A step that reports on ctx itself -- the
+// file sketching of multi.cpp -- returns before the frame.)  Which member
+// holds a copy of the message is not part of the contract.
+inline gg_status use_device(gg_ctx* c, gg_ctx* report = nullptr) {
+  return hipSetDevice(c->device) == hipSuccess ? GG_OK : fail(report ? report : c, GG_ERR_HIP, "hipSetDevice failed");
+}
 template <typename OnFailure>
 gg_status finish_call(gg_ctx* ctx, gg_ctx* pm, gg_status st, const OnFailure& on_failure) {
   if (st != GG_OK) {
@@ -337,6 +345,9 @@ gg_status finish_call(gg_ctx* ctx, gg_ctx* pm, gg_status st, const OnFailure& on
     if (pm != ctx) ctx->err = pm->err;
   }
   return st;
+}
+inline gg_status finish_call(gg_ctx* ctx, gg_ctx* pm, gg_status st) {
+  return finish_call(ctx, pm, st, [] {});
 }
 // The pair form of the product (ani_matrix.hip, matrix_core.hpp): the passing
 // pairs of the prepared positions appended to d_out, gg_pairs_device's output
@@ -382,10 +393,15 @@ gg_status border_routed_append(gg_ctx* c, const char* who, const uint64_t* d_sk,
 void count_pairs_path(gg_ctx* c, bool matrix);
 // The sized passes of a pair producer into scratch `key`: the first at `cap`,
 // one retry at the exact count.  run(d_out, cap, d_count) enqueues it on st.
-// (resident.cpp's calls and the collection's border, collection.cpp)
+// Every caller sizes through it: pairs_range_to_host (api.cpp, `who` empty:
+// its messages carry no prefix), resident.cpp's calls and the collection's
+// border (collection.cpp).  Any count up to `all` is returned: a caller whose
+// next step takes an int count (the device sort, the ANI kernel) refuses 2^31
+// pairs or more itself.  Synchronises st.
 template <typename Run>
 gg_status sized_pair_passes(gg_ctx* c, const std::string& who, const char* key, uint64_t all, uint64_t cap,
                             const Run& run, gg_pair** d_pairs, uint64_t* n_pairs, uint32_t* n_passes, hipStream_t st) {
+  const std::string w = who.empty() ? who : who + ": ";
   gg_pair* d_out = nullptr;
   uint64_t cnt = 0;
   uint32_t passes = 0;
@@ -393,7 +409,7 @@ gg_status sized_pair_passes(gg_ctx* c, const std::string& who, const char* key, 
   GG_HIP(c, scratch_t(c, "rs_count", 1, &d_count));
   GG_HIP(c, host_scratch_t(c, "rs_count", 1, &h_count));
   for (;;) {
-    if (passes == 2) return fail(c, GG_ERR_INTERNAL, who + ": pair output sizing failed");
+    if (passes == 2) return fail(c, GG_ERR_INTERNAL, w + "pair output sizing failed");
     GG_HIP(c, scratch_t(c, key, (size_t)(cap > 1 ? cap : 1), &d_out));
     GG_HIP(c, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
     const gg_status ps = run(d_out, cap, d_count);
@@ -402,21 +418,26 @@ gg_status sized_pair_passes(gg_ctx* c, const std::string& who, const char* key, 
     GG_HIP(c, hipMemcpyAsync(h_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     GG_HIP(c, hipStreamSynchronize(st));
     cnt = *h_count;
-    if (cnt > all) return fail(c, GG_ERR_INTERNAL, who + ": bad pair count");
+    if (cnt > all) return fail(c, GG_ERR_INTERNAL, w + "bad pair count");
     if (cnt <= cap) break;
     cap = cnt;
   }
-  if (cnt >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, who + ": 2^31 pairs or more");
   *d_pairs = d_out;
   *n_pairs = cnt;
   *n_passes = passes;
   return GG_OK;
 }
-// The rows of a file list on the first member's device (multi.cpp): sketched
-// by sketch_files_members (cache and errors as gg_sketch_files; a multi-device
-// context sketches on every member, the rows then go to the first through the
-// host, as gg_precluster_files_resident).  *d_sk / *d_len: context scratch of
-// the first member, valid until its next call.  Synchronises its stream.
+// The files-to-rows step of every call that needs a file list's rows on the
+// first member's device (multi.cpp: gg_precluster_files_resident,
+// gg_precluster_matrices_files, gg_cluster_files_resident on one device;
+// collection.cpp: gg_collection_add_files).  The phases are reset, the files
+// sketched by sketch_files_members (cache and errors as gg_sketch_files) and
+// GG_PHASE_SKETCH stamped; a multi-device context sketches on every member and
+// the rows then go to the first through the host (scratch mx_h_sk / mx_h_len,
+// its stream synchronised).  The first member's device is current afterwards.
+// *d_sk / *d_len: context scratch of the first member, valid until its next
+// call; n == 0: both null.  Every failure is reported on ctx: a caller returns
+// it as it is, before its own frame.
 gg_status sketch_files_first(gg_ctx* ctx, const char* const* paths, uint32_t n, const char* cache_dir,
                              const uint64_t** d_sk, const uint32_t** d_len);
 // Rows resident -> rep_of resident (resident.cpp): K2 into context scratch,
@@ -526,11 +547,26 @@ void gz_settle_errors(GzClaims& cl);
 // host, else when one of its first files is gzip (by its magic bytes).
 bool gz_device_list(const char* const* paths, uint32_t n);
 
+// A call's library-owned outputs (gg_free): max(count, 1) elements holding a
+// host vector (null: out of memory), or the first cnt elements of a device
+// array, their copy enqueued on st; free_out frees and nulls those of a call
+// that fails after it made them (its on_failure; null arguments are skipped).
 template <typename T>
 T* copy_out(const std::vector<T>& v) {
   T* p = (T*)malloc(std::max<size_t>(v.size(), 1) * sizeof(T));
   if (p && !v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
   return p;
+}
+template <typename T>
+gg_status copy_out(gg_ctx* c, const T* d_src, uint64_t cnt, T** out, hipStream_t st) {
+  *out = (T*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(T));
+  if (!*out) return fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+  if (cnt) GG_HIP(c, hipMemcpyAsync(*out, d_src, cnt * sizeof(T), hipMemcpyDeviceToHost, st));
+  return GG_OK;
+}
+template <typename... T>
+void free_out(T**... out) {
+  ((out ? (free(*out), *out = nullptr, 0) : 0), ...);
 }
 
 }  // namespace gg

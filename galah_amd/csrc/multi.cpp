@@ -54,11 +54,8 @@ template <class F>
 gg_status on_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, F&& f) {
   std::vector<gg_status> st(ms.size(), GG_OK);
   const std::function<void(size_t)> run = [&](size_t i) {
-    if (hipSetDevice(ms[i]->device) != hipSuccess) {
-      st[i] = fail(ms[i], GG_ERR_HIP, "hipSetDevice failed");
-      return;
-    }
-    st[i] = f(i, ms[i]);
+    st[i] = use_device(ms[i]);
+    if (st[i] == GG_OK) st[i] = f(i, ms[i]);
   };
   if (ms.size() == 1) {
     run(0);
@@ -259,10 +256,7 @@ gg_status pairs_with_ani(gg_ctx* c, const std::vector<gg_pair>& res, gg_pair** p
   *pairs = copy_out(res);
   *ani = (float*)malloc(std::max<size_t>(m, 1) * sizeof(float));
   if (!*pairs || !*ani) {
-    free(*pairs);
-    free(*ani);
-    *pairs = nullptr;
-    *ani = nullptr;
+    free_out(pairs, ani);
     return fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
   }
   float* a = *ani;
@@ -809,7 +803,7 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
     all.insert(all.end(), hit_spans.begin(), hit_spans.end());
     for (const RowSpan& sp : all) {
       gg_ctx* o = ms[sp.owner];
-      if (hipSetDevice(o->device) != hipSuccess) return fail(c, GG_ERR_HIP, "hipSetDevice failed");
+      if (use_device(o, c) != GG_OK) return GG_ERR_HIP;
       if (host_out)
         GG_HIP(c, hipMemcpyAsync(host_out + (size_t)sp.row0 * s, rows[sp.owner].sk + (size_t)sp.row0 * s,
                                  (size_t)sp.rows * s * sizeof(uint64_t), hipMemcpyDeviceToHost, o->stream));
@@ -818,7 +812,7 @@ gg_status sketch_files_members(gg_ctx* c, const std::vector<gg_ctx*>& ms, const 
                                  hipMemcpyDeviceToHost, o->stream));
     }
     for (gg_ctx* o : ms) {
-      if (hipSetDevice(o->device) != hipSuccess) return fail(c, GG_ERR_HIP, "hipSetDevice failed");
+      if (use_device(o, c) != GG_OK) return GG_ERR_HIP;
       GG_HIP(c, hipStreamSynchronize(o->stream));
     }
   }
@@ -859,37 +853,44 @@ std::vector<uint32_t> balance_genomes(const gg_run* runs, uint64_t n_runs, uint3
 
 }  // namespace
 
+// n > 0 rows on the host to scratch of m, the first member
+static gg_status rows_to_first(gg_ctx* m, const std::vector<uint64_t>& h_sk, const std::vector<uint32_t>& h_len, uint32_t n,
+                               const uint64_t** d_sk, const uint32_t** d_len) {
+  const size_t s = m->s;
+  uint64_t* up_sk;
+  uint32_t* up_len;
+  GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)n * s, &up_sk));
+  GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)n, &up_len));
+  GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
+  GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
+  GG_HIP(m, hipStreamSynchronize(m->stream));  // (the staging vectors end with the call)
+  *d_sk = up_sk;
+  *d_len = up_len;
+  return GG_OK;
+}
+
 gg_status sketch_files_first(gg_ctx* ctx, const char* const* paths, uint32_t n, const char* cache_dir,
                              const uint64_t** d_sk, const uint32_t** d_len) {
+  for (double& x : ctx->phase_ms) x = 0.0;
   const std::vector<gg_ctx*> ms = members(ctx);
   gg_ctx* m = ms[0];
-  const uint32_t s = m->s;
+  const bool staged = ms.size() > 1;  // sketched on every member: the rows go to the first through the host
+  const size_t s = m->s;
   std::vector<Rows> rows;
   std::vector<RowSpan> spans;
-  std::vector<uint64_t> h_sk;
-  std::vector<uint32_t> h_len;
-  if (ms.size() > 1) {
-    h_sk.resize((size_t)std::max(n, 1u) * s);
-    h_len.resize(std::max(n, 1u));
-  }
-  const gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, ms.size() > 1 ? h_sk.data() : nullptr,
-                                            ms.size() > 1 ? h_len.data() : nullptr, nullptr);
+  std::vector<uint64_t> h_sk(staged ? std::max<size_t>(n, 1) * s : 0);
+  std::vector<uint32_t> h_len(staged ? std::max(n, 1u) : 0);
+  const auto t0 = Clock::now();
+  // (every file is read and sketched, even a lone one: gg_precluster_files_cached)
+  gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, staged ? h_sk.data() : nullptr,
+                                      staged ? h_len.data() : nullptr, nullptr);
   if (st != GG_OK) return st;
-  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  *d_sk = rows[0].sk;
-  *d_len = rows[0].len;
-  if (ms.size() > 1) {
-    uint64_t* up_sk;
-    uint32_t* up_len;
-    GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)std::max(n, 1u) * s, &up_sk));
-    GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)std::max(n, 1u), &up_len));
-    GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-    GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-    *d_sk = up_sk;
-    *d_len = up_len;
-  }
-  GG_HIP(m, hipStreamSynchronize(m->stream));
-  return GG_OK;
+  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
+  *d_sk = n ? rows[0].sk : nullptr;
+  *d_len = n ? rows[0].len : nullptr;
+  st = use_device(m);
+  if (st == GG_OK && n && staged) st = rows_to_first(m, h_sk, h_len, n, d_sk, d_len);
+  return finish_call(ctx, m, st);
 }
 
 }  // namespace gg
@@ -1115,28 +1116,41 @@ gg_status gg_sketch_files_stats(gg_ctx* ctx, const char* const* paths, uint32_t 
                               out_stats);
 }
 
-gg_status gg_precluster_files_cached(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
-                                     const char* cache_dir, gg_pair** pairs, float** ani, uint64_t* n_out,
-                                     uint32_t* n_cached) {
-  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
-  if (!pairs || !ani || !n_out || (n_paths && !paths))
-    return fail(ctx, GG_ERR_INVALID_ARG, "gg_precluster_files: null argument");
+// What gg_precluster_files_cached and gg_precluster_files_each share before
+// their pairs: the argument checks (bad: a null argument of the caller's own),
+// the outputs and the phases reset, the files sketched on every member (rows and
+// spans per member, for gather_pairs_merge) and GG_PHASE_SKETCH stamped.
+static gg_status precluster_files_rows(gg_ctx* ctx, const char* who, bool bad, const std::vector<gg_ctx*>& ms,
+                                       const char* const* paths, uint32_t n_paths, float min_ani, const char* cache_dir,
+                                       gg_pair** pairs, float** ani, uint64_t* n_out, uint32_t* n_cached,
+                                       std::vector<Rows>& rows, std::vector<RowSpan>& spans) {
+  if (bad || !pairs || !ani || !n_out || (n_paths && !paths))
+    return fail(ctx, GG_ERR_INVALID_ARG, std::string(who) + ": null argument");
   if (std::isnan(min_ani)) return fail(ctx, GG_ERR_INVALID_ARG, "min_ani is NaN");
   *pairs = nullptr;
   *ani = nullptr;
   *n_out = 0;
   if (n_cached) *n_cached = 0;
   for (double& x : ctx->phase_ms) x = 0.0;
+  const auto t0 = Clock::now();
+  // every file is read and sketched, even a lone one: a file that does not
+  // parse fails the call as finch's sketch_files does (src/finch.rs:50)
+  const gg_status st = sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, nullptr, nullptr, n_cached);
+  if (st == GG_OK) ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
+  return st;
+}
+
+gg_status gg_precluster_files_cached(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
+                                     const char* cache_dir, gg_pair** pairs, float** ani, uint64_t* n_out,
+                                     uint32_t* n_cached) {
+  if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   const std::vector<gg_ctx*> ms = members(ctx);
   std::vector<Rows> rows;
   std::vector<RowSpan> spans;
   std::vector<gg_pair> res;
-  auto t0 = Clock::now();
-  // every file is read and sketched, even a lone one: a file that does not
-  // parse fails the call as finch's sketch_files does (src/finch.rs:50)
-  gg_status st = sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, nullptr, nullptr, n_cached);
+  gg_status st = precluster_files_rows(ctx, "gg_precluster_files", false, ms, paths, n_paths, min_ani, cache_dir, pairs, ani,
+                                       n_out, n_cached, rows, spans);
   if (st != GG_OK) return st;
-  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
   if (n_paths >= 2) {
     st = gather_pairs_merge(ctx, ms, rows, spans, n_paths, min_ani, res);
     if (st != GG_OK) return st;
@@ -1147,6 +1161,18 @@ gg_status gg_precluster_files_cached(gg_ctx* ctx, const char* const* paths, uint
 gg_status gg_precluster_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
                               gg_pair** pairs, float** ani, uint64_t* n_out) {
   return gg_precluster_files_cached(ctx, paths, n_paths, min_ani, nullptr, pairs, ani, n_out, nullptr);
+}
+
+// gg_cluster_files_resident on one device, its rows resident: rep_of of them
+static gg_status cluster_files_rows(gg_ctx* m, const uint64_t* d_sk, const uint32_t* d_len, uint32_t n, float min_ani,
+                                    float cluster_ani, uint32_t* rep_of, gg_cluster_summary* summary) {
+  uint32_t* d_rep = nullptr;
+  GG_HIP(m, scratch_t(m, "rs_rep", (size_t)n, &d_rep));
+  const gg_status st = cluster_rows_device(m, d_sk, d_len, n, min_ani, cluster_ani, d_rep, summary, nullptr, nullptr, m->stream);
+  if (st != GG_OK) return st;
+  GG_HIP(m, hipMemcpyAsync(rep_of, d_rep, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  return GG_OK;
 }
 
 gg_status gg_cluster_files_resident(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
@@ -1181,29 +1207,38 @@ gg_status gg_cluster_files_resident(gg_ctx* ctx, const char* const* paths, uint3
     gg_free(a);
     return st;
   }
-  for (double& x : ctx->phase_ms) x = 0.0;
-  std::vector<Rows> rows;
-  std::vector<RowSpan> spans;
-  auto t0 = Clock::now();
-  // (every file is read and sketched, even a lone one: gg_precluster_files_cached)
-  gg_status st = sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, nullptr, nullptr, nullptr);
-  if (st != GG_OK) return st;
-  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
-  if (n_paths == 0) return GG_OK;
-  t0 = Clock::now();
+  const uint64_t* d_sk = nullptr;
+  const uint32_t* d_len = nullptr;
+  gg_status st = sketch_files_first(ctx, paths, n_paths, cache_dir, &d_sk, &d_len);
+  if (st != GG_OK || n_paths == 0) return st;
+  const auto t0 = Clock::now();
   gg_ctx* m = ms[0];
-  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  uint32_t* d_rep = nullptr;
-  GG_HIP(m, scratch_t(m, "rs_rep", (size_t)n_paths, &d_rep));
-  st = cluster_rows_device(m, rows[0].sk, rows[0].len, n_paths, min_ani, cluster_ani, d_rep, summary, nullptr, nullptr,
-                           m->stream);
-  if (st != GG_OK) {
-    if (summary) *summary = gg_cluster_summary{};
-    return st;
-  }
-  GG_HIP(m, hipMemcpyAsync(rep_of, d_rep, (size_t)n_paths * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  st = cluster_files_rows(m, d_sk, d_len, n_paths, min_ani, cluster_ani, rep_of, summary);
+  if (st == GG_OK) ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
+  return finish_call(ctx, m, st, [&] { if (summary) *summary = gg_cluster_summary{}; });
+}
+
+// gg_precluster_files_resident with its n rows resident on m: the pairs by the
+// context's path, sorted by (i, j), and their f32 ANI; only these come back
+static gg_status precluster_rows(gg_ctx* m, const char* who, const uint64_t* d_sk, const uint32_t* d_len, uint32_t n,
+                                 float min_ani, gg_pair** pairs, float** ani, uint64_t* n_out,
+                                 gg_pairs_matrix_summary* summary) {
+  gg_pair *d_pairs = nullptr, *d_sorted = nullptr;
+  float* d_val = nullptr;
+  uint64_t cnt = 0;
+  uint32_t passes = 0;
+  gg_status r = pairs_rows_device(m, who, d_sk, d_len, n, min_ani, &d_pairs, &cnt, &passes, m->stream, summary);
+  if (r != GG_OK) return r;
+  r = sorted_pairs_device(m, d_pairs, cnt, n, &d_sorted, m->stream);
+  if (r != GG_OK) return r;
+  GG_HIP(m, scratch_t(m, "rs_ani", (size_t)std::max<uint64_t>(cnt, 1), &d_val));
+  r = ani_f32_device(m, d_sorted, cnt, d_val, nullptr, nullptr, m->stream);
+  if (r != GG_OK) return r;
+  r = copy_out(m, d_sorted, cnt, pairs, m->stream);
+  if (r == GG_OK) r = copy_out(m, d_val, cnt, ani, m->stream);
+  if (r != GG_OK) return r;
   GG_HIP(m, hipStreamSynchronize(m->stream));
-  ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
+  *n_out = cnt;
   return GG_OK;
 }
 
@@ -1219,75 +1254,81 @@ gg_status gg_precluster_files_resident(gg_ctx* ctx, const char* const* paths, ui
   *pairs = nullptr;
   *ani = nullptr;
   *n_out = 0;
-  for (double& x : ctx->phase_ms) x = 0.0;
-  const std::vector<gg_ctx*> ms = members(ctx);
-  gg_ctx* m = ms[0];
-  const uint32_t n = n_paths, s = m->s;
-  std::vector<Rows> rows;
-  std::vector<RowSpan> spans;
-  // a multi-device context sketches on every member; the rows then go to the first through the host
-  std::vector<uint64_t> h_sk;
-  std::vector<uint32_t> h_len;
-  if (ms.size() > 1) {
-    h_sk.resize((size_t)std::max(n, 1u) * s);
-    h_len.resize(std::max(n, 1u));
-  }
-  auto t0 = Clock::now();
-  // (every file is read and sketched, even a lone one: gg_precluster_files_cached)
-  gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, ms.size() > 1 ? h_sk.data() : nullptr,
-                                      ms.size() > 1 ? h_len.data() : nullptr, nullptr);
+  const uint64_t* d_sk = nullptr;
+  const uint32_t* d_len = nullptr;
+  gg_status st = sketch_files_first(ctx, paths, n_paths, cache_dir, &d_sk, &d_len);
   if (st != GG_OK) return st;
-  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
-  t0 = Clock::now();
-  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  auto run = [&]() -> gg_status {
-    const uint64_t* d_sk = n ? rows[0].sk : nullptr;
-    const uint32_t* d_len = n ? rows[0].len : nullptr;
-    if (n && ms.size() > 1) {
-      uint64_t* up_sk;
-      uint32_t* up_len;
-      GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)n * s, &up_sk));
-      GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)n, &up_len));
-      GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-      GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-      d_sk = up_sk;
-      d_len = up_len;
-    }
-    // the pairs by the context's path, sorted by (i, j), and their f32 ANI, all on the resident rows
-    gg_pair *d_pairs = nullptr, *d_sorted = nullptr;
-    float* d_val = nullptr;
-    uint64_t cnt = 0;
-    uint32_t passes = 0;
-    gg_status r = pairs_rows_device(m, who, d_sk, d_len, n, min_ani, &d_pairs, &cnt, &passes, m->stream, summary);
-    if (r != GG_OK) return r;
-    r = sorted_pairs_device(m, d_pairs, cnt, n, &d_sorted, m->stream);
-    if (r != GG_OK) return r;
-    GG_HIP(m, scratch_t(m, "rs_ani", (size_t)std::max<uint64_t>(cnt, 1), &d_val));
-    r = ani_f32_device(m, d_sorted, cnt, d_val, nullptr, nullptr, m->stream);
-    if (r != GG_OK) return r;
-    *pairs = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
-    *ani = (float*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(float));
-    if (!*pairs || !*ani) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-    if (cnt) {
-      GG_HIP(m, hipMemcpyAsync(*pairs, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, m->stream));
-      GG_HIP(m, hipMemcpyAsync(*ani, d_val, cnt * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-    }
-    GG_HIP(m, hipStreamSynchronize(m->stream));
-    *n_out = cnt;
-    return GG_OK;
-  };
-  st = run();
+  gg_ctx* m = primary(ctx);
+  const auto t0 = Clock::now();
+  st = precluster_rows(m, who, d_sk, d_len, n_paths, min_ani, pairs, ani, n_out, summary);
   ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
-  if (st != GG_OK) {
-    free(*pairs);
-    free(*ani);
-    *pairs = nullptr;
-    *ani = nullptr;
+  return finish_call(ctx, m, st, [&] {
+    free_out(pairs, ani);
     *n_out = 0;
     if (summary) *summary = gg_pairs_matrix_summary{};
-    if (m != ctx) ctx->err = m->err;
+  });
+}
+
+// gg_precluster_matrices_files with its n rows resident on m: K2, the
+// partition of its pair list and the groups' matrices; only the results come back
+static gg_status precluster_matrices_rows(gg_ctx* m, const char* who, const uint64_t* d_sk, const uint32_t* d_len, uint32_t n,
+                                          float min_ani, uint32_t** members, uint32_t** offsets, uint32_t* n_groups,
+                                          uint64_t** cell_offsets, uint32_t** common, uint32_t** total, float** ani,
+                                          gg_matrix_summary* summary) {
+  gg_pair* d_pairs = nullptr;
+  uint64_t n_pairs = 0;
+  uint32_t passes = 0, n_sets = 0;
+  gg_status r = pairs_rows_device(m, who, d_sk, d_len, n, min_ani, &d_pairs, &n_pairs, &passes, m->stream);
+  if (r != GG_OK) return r;
+  uint32_t *d_members = nullptr, *d_offsets = nullptr;
+  GG_HIP(m, scratch_t(m, "rs_members", (size_t)std::max(n, 1u), &d_members));
+  GG_HIP(m, scratch_t(m, "rs_offsets", (size_t)n + 1, &d_offsets));
+  if (n) {
+    r = preclusters_device(m, n, d_pairs, n_pairs, d_members, d_offsets, &n_sets, nullptr, nullptr, m->stream);
+    if (r != GG_OK) return r;
   }
-  return st;
+  *members = (uint32_t*)malloc(std::max<size_t>(n, 1) * sizeof(uint32_t));
+  *offsets = (uint32_t*)calloc((size_t)n_sets + 1, sizeof(uint32_t));
+  *cell_offsets = (uint64_t*)calloc((size_t)n_sets + 1, sizeof(uint64_t));
+  if (!*members || !*offsets || !*cell_offsets) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+  if (n) {
+    GG_HIP(m, hipMemcpyAsync(*members, d_members, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+    GG_HIP(m, hipMemcpyAsync(*offsets, d_offsets, ((size_t)n_sets + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                             m->stream));
+    GG_HIP(m, hipStreamSynchronize(m->stream));
+  }
+  r = gg_ani_matrix_group_cells(*offsets, n_sets, *cell_offsets);
+  if (r != GG_OK) return fail(m, r, gg_thread_last_error());
+  const uint64_t cells = (*cell_offsets)[n_sets];
+  uint32_t *d_common = nullptr, *d_total = nullptr;
+  float* d_ani = nullptr;
+  if (common) {
+    *common = (uint32_t*)malloc(std::max<uint64_t>(cells, 1) * sizeof(uint32_t));
+    if (!*common) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+    GG_HIP(m, scratch_t(m, "mx_h_common", (size_t)cells, &d_common));
+  }
+  if (total) {
+    *total = (uint32_t*)malloc(std::max<uint64_t>(cells, 1) * sizeof(uint32_t));
+    if (!*total) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+    GG_HIP(m, scratch_t(m, "mx_h_total", (size_t)cells, &d_total));
+  }
+  if (ani) {
+    *ani = (float*)malloc(std::max<uint64_t>(cells, 1) * sizeof(float));
+    if (!*ani) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
+    GG_HIP(m, scratch_t(m, "mx_h_ani", (size_t)cells, &d_ani));
+  }
+  if (cells == 0) {
+    *n_groups = n_sets;
+    return GG_OK;
+  }
+  r = ani_matrix_groups_device(m, d_sk, d_len, n, d_members, *offsets, n_sets, d_common, d_total, d_ani, summary, m->stream);
+  if (r != GG_OK) return r;
+  if (common) GG_HIP(m, hipMemcpyAsync(*common, d_common, cells * 4, hipMemcpyDeviceToHost, m->stream));
+  if (total) GG_HIP(m, hipMemcpyAsync(*total, d_total, cells * 4, hipMemcpyDeviceToHost, m->stream));
+  if (ani) GG_HIP(m, hipMemcpyAsync(*ani, d_ani, cells * 4, hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  *n_groups = n_sets;
+  return GG_OK;
 }
 
 gg_status gg_precluster_matrices_files(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
@@ -1307,136 +1348,33 @@ gg_status gg_precluster_matrices_files(gg_ctx* ctx, const char* const* paths, ui
   if (common) *common = nullptr;
   if (total) *total = nullptr;
   if (ani) *ani = nullptr;
-  for (double& x : ctx->phase_ms) x = 0.0;
-  const std::vector<gg_ctx*> ms = gg::members(ctx);  // (the parameter `members` hides the function)
-  gg_ctx* m = ms[0];
-  const uint32_t n = n_paths, s = m->s;
-  std::vector<Rows> rows;
-  std::vector<RowSpan> spans;
-  // a multi-device context sketches on every member; the rows then go to the first through the host
-  std::vector<uint64_t> h_sk;
-  std::vector<uint32_t> h_len;
-  if (ms.size() > 1) {
-    h_sk.resize((size_t)std::max(n, 1u) * s);
-    h_len.resize(std::max(n, 1u));
-  }
-  auto t0 = Clock::now();
-  gg_status st = sketch_files_members(ctx, ms, paths, n, cache_dir, rows, spans, ms.size() > 1 ? h_sk.data() : nullptr,
-                                      ms.size() > 1 ? h_len.data() : nullptr, nullptr);
+  const uint64_t* d_sk = nullptr;
+  const uint32_t* d_len = nullptr;
+  gg_status st = sketch_files_first(ctx, paths, n_paths, cache_dir, &d_sk, &d_len);
   if (st != GG_OK) return st;
-  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
-  t0 = Clock::now();
-  if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
-  const uint64_t* d_sk = n ? rows[0].sk : nullptr;
-  const uint32_t* d_len = n ? rows[0].len : nullptr;
-  auto run = [&]() -> gg_status {
-    if (n && ms.size() > 1) {
-      uint64_t* up_sk;
-      uint32_t* up_len;
-      GG_HIP(m, scratch_t(m, "mx_h_sk", (size_t)n * s, &up_sk));
-      GG_HIP(m, scratch_t(m, "mx_h_len", (size_t)n, &up_len));
-      GG_HIP(m, hipMemcpyAsync(up_sk, h_sk.data(), (size_t)n * s * sizeof(uint64_t), hipMemcpyHostToDevice, m->stream));
-      GG_HIP(m, hipMemcpyAsync(up_len, h_len.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-      d_sk = up_sk;
-      d_len = up_len;
-    }
-    // K2, the partition of its pair list and the groups' matrices, all on the resident rows
-    gg_pair* d_pairs = nullptr;
-    uint64_t n_pairs = 0;
-    uint32_t passes = 0, n_sets = 0;
-    gg_status r = pairs_rows_device(m, who, d_sk, d_len, n, min_ani, &d_pairs, &n_pairs, &passes, m->stream);
-    if (r != GG_OK) return r;
-    uint32_t *d_members = nullptr, *d_offsets = nullptr;
-    GG_HIP(m, scratch_t(m, "rs_members", (size_t)std::max(n, 1u), &d_members));
-    GG_HIP(m, scratch_t(m, "rs_offsets", (size_t)n + 1, &d_offsets));
-    if (n) {
-      r = preclusters_device(m, n, d_pairs, n_pairs, d_members, d_offsets, &n_sets, nullptr, nullptr, m->stream);
-      if (r != GG_OK) return r;
-    }
-    *members = (uint32_t*)malloc(std::max<size_t>(n, 1) * sizeof(uint32_t));
-    *offsets = (uint32_t*)calloc((size_t)n_sets + 1, sizeof(uint32_t));
-    *cell_offsets = (uint64_t*)calloc((size_t)n_sets + 1, sizeof(uint64_t));
-    if (!*members || !*offsets || !*cell_offsets) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-    if (n) {
-      GG_HIP(m, hipMemcpyAsync(*members, d_members, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-      GG_HIP(m, hipMemcpyAsync(*offsets, d_offsets, ((size_t)n_sets + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                               m->stream));
-      GG_HIP(m, hipStreamSynchronize(m->stream));
-    }
-    r = gg_ani_matrix_group_cells(*offsets, n_sets, *cell_offsets);
-    if (r != GG_OK) return fail(m, r, gg_thread_last_error());
-    const uint64_t cells = (*cell_offsets)[n_sets];
-    uint32_t *d_common = nullptr, *d_total = nullptr;
-    float* d_ani = nullptr;
-    if (common) {
-      *common = (uint32_t*)malloc(std::max<uint64_t>(cells, 1) * sizeof(uint32_t));
-      if (!*common) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-      GG_HIP(m, scratch_t(m, "mx_h_common", (size_t)cells, &d_common));
-    }
-    if (total) {
-      *total = (uint32_t*)malloc(std::max<uint64_t>(cells, 1) * sizeof(uint32_t));
-      if (!*total) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-      GG_HIP(m, scratch_t(m, "mx_h_total", (size_t)cells, &d_total));
-    }
-    if (ani) {
-      *ani = (float*)malloc(std::max<uint64_t>(cells, 1) * sizeof(float));
-      if (!*ani) return fail(m, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-      GG_HIP(m, scratch_t(m, "mx_h_ani", (size_t)cells, &d_ani));
-    }
-    if (cells == 0) {
-      *n_groups = n_sets;
-      return GG_OK;
-    }
-    r = ani_matrix_groups_device(m, d_sk, d_len, n, d_members, *offsets, n_sets, d_common, d_total, d_ani, summary,
-                                 m->stream);
-    if (r != GG_OK) return r;
-    if (common) GG_HIP(m, hipMemcpyAsync(*common, d_common, cells * 4, hipMemcpyDeviceToHost, m->stream));
-    if (total) GG_HIP(m, hipMemcpyAsync(*total, d_total, cells * 4, hipMemcpyDeviceToHost, m->stream));
-    if (ani) GG_HIP(m, hipMemcpyAsync(*ani, d_ani, cells * 4, hipMemcpyDeviceToHost, m->stream));
-    GG_HIP(m, hipStreamSynchronize(m->stream));
-    *n_groups = n_sets;
-    return GG_OK;
-  };
-  st = run();
+  gg_ctx* m = primary(ctx);
+  const auto t0 = Clock::now();
+  st = precluster_matrices_rows(m, who, d_sk, d_len, n_paths, min_ani, members, offsets, n_groups, cell_offsets, common,
+                                total, ani, summary);
   ctx->phase_ms[GG_PHASE_PAIRS] = ms_since(t0);
-  if (st != GG_OK) {
-    free(*members);
-    free(*offsets);
-    free(*cell_offsets);
-    *members = *offsets = nullptr;
-    *cell_offsets = nullptr;
-    for (void** p : {(void**)common, (void**)total, (void**)ani})
-      if (p) {
-        free(*p);
-        *p = nullptr;
-      }
+  return finish_call(ctx, m, st, [&] {
+    free_out(members, offsets, cell_offsets, common, total, ani);
     *n_groups = 0;
     if (summary) *summary = gg_matrix_summary{};
-    if (m != ctx) ctx->err = m->err;
-  }
-  return st;
+  });
 }
 
 gg_status gg_precluster_files_each(gg_ctx* ctx, const char* const* paths, uint32_t n_paths, float min_ani,
                                    const char* cache_dir, gg_pair_sink sink, void* user, gg_pair** pairs,
                                    float** ani, uint64_t* n_out, uint32_t* n_cached) {
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
-  if (!sink || !pairs || !ani || !n_out || (n_paths && !paths))
-    return fail(ctx, GG_ERR_INVALID_ARG, "gg_precluster_files_each: null argument");
-  if (std::isnan(min_ani)) return fail(ctx, GG_ERR_INVALID_ARG, "min_ani is NaN");
-  *pairs = nullptr;
-  *ani = nullptr;
-  *n_out = 0;
-  if (n_cached) *n_cached = 0;
-  for (double& x : ctx->phase_ms) x = 0.0;
   const std::vector<gg_ctx*> ms = members(ctx);
   std::vector<Rows> rows;
   std::vector<RowSpan> spans;
   std::vector<gg_pair> res;
-  auto t0 = Clock::now();
-  gg_status st = sketch_files_members(ctx, ms, paths, n_paths, cache_dir, rows, spans, nullptr, nullptr, n_cached);
+  gg_status st = precluster_files_rows(ctx, "gg_precluster_files_each", !sink, ms, paths, n_paths, min_ani, cache_dir, pairs,
+                                       ani, n_out, n_cached, rows, spans);
   if (st != GG_OK) return st;
-  ctx->phase_ms[GG_PHASE_SKETCH] = ms_since(t0);
   if (n_paths >= 2) {
     // the passing pairs as gg_precluster_files finds them (the index K2);
     // afterwards every member holds every row
@@ -1450,7 +1388,7 @@ gg_status gg_precluster_files_each(gg_ctx* ctx, const char* const* paths, uint32
     if (const char* e = getenv("GALAHGPU_EACH_PAIRS"))  // (tests: smaller blocks)
       if (atoll(e) > 0) kEachPairs = (uint64_t)atoll(e);
     gg_ctx* m = ms[0];
-    if (hipSetDevice(m->device) != hipSuccess) return fail(ctx, GG_ERR_HIP, "hipSetDevice failed");
+    if (use_device(m, ctx) != GG_OK) return GG_ERR_HIP;
     const uint64_t n = n_paths, nb = (n + GG_PAIR_TILE - 1) / GG_PAIR_TILE;
     auto row_tile = [&](uint64_t I) { return I * nb - I * (I - 1) / 2; };  // first tile of tile row I
     std::vector<gg_pair> blk;
@@ -1463,10 +1401,7 @@ gg_status gg_precluster_files_each(gg_ctx* ctx, const char* const* paths, uint32
       } while (b < nb && cnt < kEachPairs);
       blk.clear();
       st = pairs_range_to_host(m, rows[0].sk, rows[0].len, n_paths, row_tile(a), row_tile(b), 0.0f, blk, m->stream);
-      if (st != GG_OK) {
-        if (m != ctx) ctx->err = m->err;
-        return st;
-      }
+      if (st != GG_OK) return finish_call(ctx, m, st);
       if (sink(user, blk.data(), blk.size()) != 0)
         return fail(ctx, GG_ERR_CANCELLED, "gg_precluster_files_each: the pair sink stopped the call");
       a = b;

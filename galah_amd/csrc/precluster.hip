@@ -407,60 +407,58 @@ gg_status gg_preclusters_device(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* 
     st = fail(m, GG_ERR_INVALID_ARG, "gg_preclusters_device: null argument");
   else if (n_pairs >= (1ull << 31) || n_genomes >= (1u << 31))
     st = fail(m, GG_ERR_INVALID_ARG, "gg_preclusters_device: 2^31 pairs or genomes, or more");
-  else if (hipSetDevice(m->device) != hipSuccess)
-    st = fail(m, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(m)) == GG_OK)
     st = preclusters_device(m, n_genomes, d_pairs, n_pairs, d_members, d_offsets, n_sets, d_local, d_pair_offsets,
                             (hipStream_t)stream);
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, st);
+}
+
+// gg_preclusters behind its context lookup
+static gg_status preclusters_ctx(gg_ctx* m, uint32_t n_genomes, const gg_pair* pairs, uint64_t n_pairs, uint32_t* members,
+                                 uint32_t* offsets, uint32_t* n_sets, gg_local_pair* local, uint64_t* pair_offsets) {
+  if ((n_pairs && !pairs) || !offsets || (n_genomes && !members) || !n_sets ||
+      (pair_offsets ? (n_pairs && !local) : local != nullptr))
+    return fail(m, GG_ERR_INVALID_ARG, "gg_preclusters: null argument");
+  if (n_pairs >= (1ull << 31) || n_genomes >= (1u << 31))
+    return fail(m, GG_ERR_INVALID_ARG, "gg_preclusters: 2^31 pairs or genomes, or more");
+  for (uint64_t p = 0; p < n_pairs; ++p)
+    if (pairs[p].i >= n_genomes || pairs[p].j >= n_genomes)
+      return fail(m, GG_ERR_INVALID_ARG, "gg_preclusters: pair index out of range");
+  gg_status st = use_device(m);
+  if (st != GG_OK) return st;
+  const uint32_t n = n_genomes;
+  gg_pair* d_pairs = nullptr;
+  uint32_t *d_members = nullptr, *d_offsets = nullptr;
+  gg_local_pair* d_local = nullptr;
+  uint64_t* d_poff = nullptr;
+  GG_HIP(m, scratch_t(m, "pc_in_pairs", (size_t)n_pairs, &d_pairs));
+  GG_HIP(m, scratch_t(m, "pc_out_members", (size_t)n, &d_members));
+  GG_HIP(m, scratch_t(m, "pc_out_offsets", (size_t)n + 1, &d_offsets));
+  if (pair_offsets) {
+    GG_HIP(m, scratch_t(m, "pc_out_local", (size_t)n_pairs, &d_local));
+    GG_HIP(m, scratch_t(m, "pc_out_poff", (size_t)n + 1, &d_poff));
+  }
+  if (n_pairs) GG_HIP(m, hipMemcpyAsync(d_pairs, pairs, n_pairs * sizeof(gg_pair), hipMemcpyHostToDevice, m->stream));
+  st = preclusters_device(m, n, d_pairs, n_pairs, d_members, d_offsets, n_sets, d_local, d_poff, m->stream);
+  if (st != GG_OK) return st;
+  const uint32_t ns = *n_sets;
+  if (n) GG_HIP(m, hipMemcpyAsync(members, d_members, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  GG_HIP(m, hipMemcpyAsync(offsets, d_offsets, ((size_t)ns + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  if (pair_offsets) {
+    if (n_pairs)
+      GG_HIP(m, hipMemcpyAsync(local, d_local, n_pairs * sizeof(gg_local_pair), hipMemcpyDeviceToHost, m->stream));
+    GG_HIP(m, hipMemcpyAsync(pair_offsets, d_poff, ((size_t)ns + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                             m->stream));
+  }
+  GG_HIP(m, hipStreamSynchronize(m->stream));
+  return GG_OK;
 }
 
 gg_status gg_preclusters(gg_ctx* ctx, uint32_t n_genomes, const gg_pair* pairs, uint64_t n_pairs, uint32_t* members,
                          uint32_t* offsets, uint32_t* n_sets, gg_local_pair* local, uint64_t* pair_offsets) {
   if (!ctx) return fail(nullptr, GG_ERR_INVALID_ARG, "null context");
   gg_ctx* m = primary(ctx);
-  auto run = [&]() -> gg_status {
-    if ((n_pairs && !pairs) || !offsets || (n_genomes && !members) || !n_sets ||
-        (pair_offsets ? (n_pairs && !local) : local != nullptr))
-      return fail(m, GG_ERR_INVALID_ARG, "gg_preclusters: null argument");
-    if (n_pairs >= (1ull << 31) || n_genomes >= (1u << 31))
-      return fail(m, GG_ERR_INVALID_ARG, "gg_preclusters: 2^31 pairs or genomes, or more");
-    for (uint64_t p = 0; p < n_pairs; ++p)
-      if (pairs[p].i >= n_genomes || pairs[p].j >= n_genomes)
-        return fail(m, GG_ERR_INVALID_ARG, "gg_preclusters: pair index out of range");
-    if (hipSetDevice(m->device) != hipSuccess) return fail(m, GG_ERR_HIP, "hipSetDevice failed");
-    const uint32_t n = n_genomes;
-    gg_pair* d_pairs = nullptr;
-    uint32_t *d_members = nullptr, *d_offsets = nullptr;
-    gg_local_pair* d_local = nullptr;
-    uint64_t* d_poff = nullptr;
-    GG_HIP(m, scratch_t(m, "pc_in_pairs", (size_t)n_pairs, &d_pairs));
-    GG_HIP(m, scratch_t(m, "pc_out_members", (size_t)n, &d_members));
-    GG_HIP(m, scratch_t(m, "pc_out_offsets", (size_t)n + 1, &d_offsets));
-    if (pair_offsets) {
-      GG_HIP(m, scratch_t(m, "pc_out_local", (size_t)n_pairs, &d_local));
-      GG_HIP(m, scratch_t(m, "pc_out_poff", (size_t)n + 1, &d_poff));
-    }
-    if (n_pairs) GG_HIP(m, hipMemcpyAsync(d_pairs, pairs, n_pairs * sizeof(gg_pair), hipMemcpyHostToDevice, m->stream));
-    const gg_status st =
-        preclusters_device(m, n, d_pairs, n_pairs, d_members, d_offsets, n_sets, d_local, d_poff, m->stream);
-    if (st != GG_OK) return st;
-    const uint32_t ns = *n_sets;
-    if (n) GG_HIP(m, hipMemcpyAsync(members, d_members, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    GG_HIP(m, hipMemcpyAsync(offsets, d_offsets, ((size_t)ns + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    if (pair_offsets) {
-      if (n_pairs)
-        GG_HIP(m, hipMemcpyAsync(local, d_local, n_pairs * sizeof(gg_local_pair), hipMemcpyDeviceToHost, m->stream));
-      GG_HIP(m, hipMemcpyAsync(pair_offsets, d_poff, ((size_t)ns + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                               m->stream));
-    }
-    GG_HIP(m, hipStreamSynchronize(m->stream));
-    return GG_OK;
-  };
-  const gg_status st = run();
-  if (st != GG_OK && m != ctx) ctx->err = m->err;
-  return st;
+  return finish_call(ctx, m, preclusters_ctx(m, n_genomes, pairs, n_pairs, members, offsets, n_sets, local, pair_offsets));
 }
 
 }  // extern "C"

@@ -3,9 +3,10 @@
 // leaving it.  What gg_pairs + gg_ani_f32 + gg_cluster_pairs give, chained
 // from their device forms:
 //
-//   1. K2 (pairs_core) over every tile into context scratch, sized as
-//      pairs_range_to_host sizes it: max(2^20, 16 n) pairs clipped to
-//      n (n - 1) / 2, the count word read back, one retry at the exact count;
+//   1. K2 (pairs_core) over every tile into context scratch, in the sized
+//      passes every caller shares (sized_pair_passes): max(2^20, 16 n) pairs
+//      clipped to n (n - 1) / 2, the count word read back, one retry at the
+//      exact count;
 //      or, by the context's pairs path (gg_set_pairs_path),
 //      the pair form of the matrix product, sized the same way;
 //   2. no sort: neither the clustering rules nor the partition depend on the
@@ -125,6 +126,7 @@ gg_status pairs_form_sorted(gg_ctx* c, const char* who, const PairsForm& form, c
       [&](gg_pair* d_out, uint64_t pcap, uint64_t* d_count) { return form.run(c, d_sk, prep, min_ani, d_out, pcap, d_count, st); },
       &d_pairs, cnt, passes, st);
   if (r != GG_OK) return r;
+  if (*cnt >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 pairs or more");
   return sorted_pairs_device(c, d_pairs, *cnt, n, d_sorted, st);
 }
 
@@ -166,11 +168,12 @@ gg_status pairs_form_host(gg_ctx* c, const char* who, const PairsForm& form, con
     *out = (gg_pair*)malloc(sizeof(gg_pair));
     return *out ? GG_OK : fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
   }
-  if (hipSetDevice(c->device) != hipSuccess) return fail(c, GG_ERR_HIP, "hipSetDevice failed");
+  gg_status r = use_device(c);
+  if (r != GG_OK) return r;
   hipStream_t st = c->stream;
   uint64_t* d_sk = nullptr;
   uint32_t *d_len = nullptr, *d_rows = nullptr;
-  gg_status r = upload_sketch_rows(c, sketches, lens, n, rows, form.m, &d_sk, &d_len, &d_rows, st);
+  r = upload_sketch_rows(c, sketches, lens, n, rows, form.m, &d_sk, &d_len, &d_rows, st);
   if (r != GG_OK) return r;
   MatrixPrep prep;
   r = form.prepare(c, who, d_sk, d_len, n, d_rows, &prep, st);
@@ -180,9 +183,8 @@ gg_status pairs_form_host(gg_ctx* c, const char* who, const PairsForm& form, con
   uint32_t passes = 0;
   r = pairs_form_sorted(c, who, form, d_sk, prep, n, min_ani, &d_sorted, &cnt, &passes, st);
   if (r != GG_OK) return r;
-  *out = (gg_pair*)malloc(std::max<uint64_t>(cnt, 1) * sizeof(gg_pair));
-  if (!*out) return fail(c, GG_ERR_OUT_OF_MEMORY, "out of host memory");
-  if (cnt) GG_HIP(c, hipMemcpyAsync(*out, d_sorted, cnt * sizeof(gg_pair), hipMemcpyDeviceToHost, st));
+  r = copy_out(c, d_sorted, cnt, out, st);
+  if (r != GG_OK) return r;
   GG_HIP(c, hipStreamSynchronize(st));
   *n_out = cnt;
   if (sum) form.fill(sum, prep, cnt, passes);
@@ -256,6 +258,7 @@ gg_status pairs_rows_device(gg_ctx* c, const char* who, const uint64_t* d_sk, co
       },
       d_pairs, n_pairs, n_passes, st);
   if (r != GG_OK) return r;
+  if (*n_pairs >= (1ull << 31)) return fail(c, GG_ERR_INVALID_ARG, std::string(who) + ": 2^31 pairs or more");
   count_pairs_path(c, matrix);
   if (msum) {
     *msum = ms;
@@ -353,9 +356,7 @@ gg_status gg_cluster_rows_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
     st = fail(m, GG_ERR_INVALID_ARG, "gg_cluster_rows_device: min_ani or cluster_ani is NaN");
   else if (n >= (1u << 31))
     st = fail(m, GG_ERR_INVALID_ARG, "gg_cluster_rows_device: 2^31 genomes or more");
-  else if (hipSetDevice(m->device) != hipSuccess)
-    st = fail(m, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(m)) == GG_OK)
     st = cluster_rows_device(m, d_sketches, d_lens, n, min_ani, cluster_ani, d_rep_of, summary, d_pairs, d_ani,
                              (hipStream_t)stream);
   return finish_call(ctx, m, st, [&] {
@@ -378,9 +379,7 @@ gg_status gg_pairs_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_matrix_device: 2^31 sketch slots or tile pairs, or more");
   else if (m >= 2 && (!d_count || (out_cap && !d_out) || (n && (!d_sketches || !d_lens))))
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_matrix_device: null buffer");
-  else if (hipSetDevice(pm->device) != hipSuccess)
-    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  else
+  else if ((st = use_device(pm)) == GG_OK)
     st = pairs_form_device(pm, "gg_pairs_matrix", PairsForm{m, false, 0}, d_sketches, d_lens, n, d_rows, min_ani, d_out,
                            out_cap, d_count, summary, (hipStream_t)stream);
   return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_pairs_matrix_summary{}; });
@@ -390,10 +389,7 @@ gg_status gg_pairs_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches, const 
 static gg_status finish_pair_list(gg_ctx* ctx, gg_ctx* pm, gg_status st, gg_pair** out, uint64_t* n_out,
                                   gg_pairs_matrix_summary* summary) {
   return finish_call(ctx, pm, st, [&] {
-    if (out) {
-      free(*out);
-      *out = nullptr;
-    }
+    free_out(out);
     if (n_out) *n_out = 0;
     if (summary) *summary = gg_pairs_matrix_summary{};
   });
@@ -424,9 +420,7 @@ gg_status gg_pairs_border_matrix_device(gg_ctx* ctx, const uint64_t* d_sketches,
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: 2^31 sketch slots or tile pairs, or more");
   else if (work && (!d_sketches || !d_lens || !d_count || (out_cap && !d_out)))
     st = fail(pm, GG_ERR_INVALID_ARG, "gg_pairs_border_matrix_device: null buffer");
-  else if (work && hipSetDevice(pm->device) != hipSuccess)
-    st = fail(pm, GG_ERR_HIP, "hipSetDevice failed");
-  else  // (no work: nothing is run, the count is left as it is)
+  else if (!work || (st = use_device(pm)) == GG_OK)  // (no work: nothing is run, the count is left as it is)
     st = pairs_form_device(pm, "gg_pairs_border_matrix", PairsForm{n, true, n_old}, d_sketches, d_lens, n, nullptr, min_ani,
                            d_out, out_cap, d_count, summary, (hipStream_t)stream);
   return finish_call(ctx, pm, st, [&] { if (summary) *summary = gg_pairs_matrix_summary{}; });
