@@ -40,7 +40,7 @@ __all__ = [
     "pairs_border_host", "PreclusterState", "relabel_pairs", "cluster_update",
     "ani_matrix_host", "ani_matrix", "write_ani_matrix",
     "ani_matrix_group_cells", "ani_matrix_groups_host", "ani_matrix_block", "precluster_ani_matrices",
-    "Collection",
+    "Collection", "query_host", "query_best_host",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -79,6 +79,9 @@ EXPORTED_SYMBOLS = (
     "gg_collection_create", "gg_collection_destroy", "gg_collection_stat", "gg_collection_load",
     "gg_collection_add_rows", "gg_collection_add_rows_device", "gg_collection_add_files", "gg_collection_remove",
     "gg_collection_cluster", "gg_collection_pairs", "gg_collection_rows", "gg_collection_view",
+    "gg_query_host", "gg_query_rows", "gg_query_rows_device", "gg_query_best_host", "gg_query_best_device",
+    "gg_collection_query_rows", "gg_collection_query_files", "gg_collection_classify_rows",
+    "gg_collection_classify_files",
 )
 
 GG_OK = 0
@@ -300,6 +303,20 @@ _sig("gg_collection_pairs", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)
 _sig("gg_collection_rows", _i32, [_vp, _vp, _vp])
 _sig("gg_collection_view", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                   ctypes.POINTER(_vp)])
+_sig("gg_query_host", _i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, ctypes.c_int, ctypes.c_float, ctypes.POINTER(_vp),
+                             ctypes.POINTER(_u64)])
+_sig("gg_query_rows", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp),
+                             ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_query_rows_device", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, ctypes.c_float, _vp, _u64, _vp, _vp])
+_sig("gg_query_best_host", _i32, [_u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp])
+_sig("gg_query_best_device", _i32, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp])
+_sig("gg_collection_query_rows", _i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                        ctypes.POINTER(_u64)])
+_sig("gg_collection_query_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, ctypes.c_float,
+                                         _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_collection_classify_rows", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp])
+_sig("gg_collection_classify_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp,
+                                            _vp])
 
 
 class _Validation(ctypes.Structure):
@@ -672,6 +689,46 @@ def pairs_border_host(sketches, lens, n_old, min_ani, k=21):
     if st != GG_OK:
         raise _thread_err(st)
     return _take_pairs(outp, cnt.value)
+
+
+def query_host(sketches, lens, q_sketches, q_lens, min_ani, k=21):
+    """The hits of queries against rows on the host (gg_query_host): every
+    cell (row i, query q) that passes at min_ani as pair (i, n + q, common,
+    total), sorted by (i, j); no query x query cell."""
+    widths = [a.shape[1] for a in (np.asarray(sketches), np.asarray(q_sketches)) if a.ndim == 2 and a.shape[0]]
+    s = int(widths[0]) if widths else 1  # (an empty side has no width of its own)
+    sk, ln, n, _ = _rows_arg(sketches, lens, s)
+    qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, s)
+    outp, cnt = _vp(), _u64()
+    st = _L.gg_query_host(_ptr(sk), _ptr(ln), n, _ptr(qs), _ptr(ql), nq, s, int(k), ctypes.c_float(min_ani),
+                          ctypes.byref(outp), ctypes.byref(cnt))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return _take_pairs(outp, cnt.value)
+
+
+def _rank_arg(rank, n):
+    if rank is None:
+        return None
+    rank = np.ascontiguousarray(rank, dtype=np.uint32).reshape(-1)
+    if len(rank) != n:
+        raise ValueError("one rank per row")
+    return rank
+
+
+def query_best_host(n, nq, pairs, ani, rank=None):
+    """Every query's best candidate (gg_query_best_host) -> (best [nq] pairs,
+    i = 0xFFFFFFFF without a candidate hit; best_ani [nq] f32).  rank [n] u32,
+    0xFFFFFFFF: no candidate; None: every row, by its index."""
+    pa, an = _pairs_ani_arg(pairs, ani)
+    rank = _rank_arg(rank, n)
+    best = np.zeros(max(nq, 1), dtype=PAIR_DTYPE)
+    best_ani = np.zeros(max(nq, 1), dtype=np.float32)
+    st = _L.gg_query_best_host(int(n), int(nq), _ptr(pa) if len(pa) else None, _ptr(an) if len(an) else None, len(pa),
+                               None if rank is None or n == 0 else _ptr(rank), _ptr(best), _ptr(best_ani))
+    if st != GG_OK:
+        raise _thread_err(st)
+    return best[:nq], best_ani[:nq]
 
 
 def validate_clusters_host(sketches, lens, clusters, ani, k=21):
@@ -1257,6 +1314,92 @@ class Context:
         if st != GG_OK:
             raise _thread_err(st)
         return tuple(x.value or 0 for x in p)
+
+    # ---- the query: hits and nearest representative of genomes that are not added (gg_query_*)
+    def query_rows(self, sketches, lens, q_sketches, q_lens, min_ani):
+        """-> (pairs (i, n + q, common, total) sorted by (i, j), ani f32) of
+        the cells (row i, query q) that pass at min_ani."""
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, self.s)
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        st = _L.gg_query_rows(self._c, _ptr(sk), _ptr(ln), n, _ptr(qs), _ptr(ql), nq, ctypes.c_float(min_ani),
+                              ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        return self._pairs_ani(pp, ap, cnt.value)
+
+    def query_rows_device(self, d_sketches, d_lens, n, d_q_sketches, d_q_lens, nq, min_ani, d_out, out_cap, d_count,
+                          stream=None):
+        """Device rows and queries (tensors or pointers): the passing cells
+        appended to d_out by pairs_device's output contract."""
+        st = _L.gg_query_rows_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), int(n), _dev_ptr(d_q_sketches),
+                                     _dev_ptr(d_q_lens), int(nq), ctypes.c_float(min_ani),
+                                     None if d_out is None else _dev_ptr(d_out), int(out_cap), _dev_ptr(d_count),
+                                     stream)
+        if st != GG_OK:
+            raise self._err(st)
+
+    def query_best_device(self, n, nq, d_pairs, d_ani, n_pairs, d_rank, d_best, d_best_ani, stream=None):
+        """Every query's best candidate from device hits (any order); d_rank may be None."""
+        st = _L.gg_query_best_device(self._c, int(n), int(nq), _dev_ptr(d_pairs), _dev_ptr(d_ani), int(n_pairs),
+                                     None if d_rank is None else _dev_ptr(d_rank), _dev_ptr(d_best),
+                                     _dev_ptr(d_best_ani), stream)
+        if st != GG_OK:
+            raise self._err(st)
+
+    def collection_query_rows(self, handle, q_sketches, q_lens, min_ani):
+        """Host queries against a collection (unchanged by it) -> (pairs, ani)."""
+        qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, self.s)
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        st = _L.gg_collection_query_rows(handle, _ptr(qs), _ptr(ql), nq, ctypes.c_float(min_ani), ctypes.byref(pp),
+                                         ctypes.byref(ap), ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        return self._pairs_ani(pp, ap, cnt.value)
+
+    def collection_query_files(self, handle, paths, min_ani, cache_dir=None, want_sketches=False):
+        """Files sketched (cache_dir as sketch_files) and queried -> (pairs,
+        ani), or (pairs, ani, sketches [nq, s], lens [nq]) with want_sketches."""
+        nq = len(paths)
+        arr = (ctypes.c_char_p * max(nq, 1))(*[os.fsencode(p) for p in paths])
+        out = np.zeros((max(nq, 1), self.s), dtype=np.uint64) if want_sketches else None
+        lens = np.zeros(max(nq, 1), dtype=np.uint32) if want_sketches else None
+        pp, ap, cnt = _vp(), _vp(), _u64()
+        st = _L.gg_collection_query_files(handle, arr, nq, None if cache_dir is None else os.fsencode(cache_dir),
+                                          ctypes.c_float(min_ani), None if out is None else _ptr(out),
+                                          None if lens is None else _ptr(lens), ctypes.byref(pp), ctypes.byref(ap),
+                                          ctypes.byref(cnt))
+        if st != GG_OK:
+            raise self._err(st)
+        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
+        return (pairs, ani, out[:nq], lens[:nq]) if want_sketches else (pairs, ani)
+
+    def collection_classify_rows(self, handle, q_sketches, q_lens, rank=None):
+        """Every host query's best candidate at the collection's min_ani -> (best [nq], best_ani [nq])."""
+        qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, self.s)
+        n = self.collection_stat(handle)[0]["n_rows"]
+        rank = _rank_arg(rank, n)
+        best = np.zeros(max(nq, 1), dtype=PAIR_DTYPE)
+        best_ani = np.zeros(max(nq, 1), dtype=np.float32)
+        st = _L.gg_collection_classify_rows(handle, _ptr(qs), _ptr(ql), nq, None if rank is None or n == 0 else _ptr(rank),
+                                            _ptr(best), _ptr(best_ani))
+        if st != GG_OK:
+            raise self._err(st)
+        return best[:nq], best_ani[:nq]
+
+    def collection_classify_files(self, handle, paths, rank=None, cache_dir=None):
+        """Every file's best candidate at the collection's min_ani -> (best [nq], best_ani [nq])."""
+        nq = len(paths)
+        arr = (ctypes.c_char_p * max(nq, 1))(*[os.fsencode(p) for p in paths])
+        n = self.collection_stat(handle)[0]["n_rows"]
+        rank = _rank_arg(rank, n)
+        best = np.zeros(max(nq, 1), dtype=PAIR_DTYPE)
+        best_ani = np.zeros(max(nq, 1), dtype=np.float32)
+        st = _L.gg_collection_classify_files(handle, arr, nq, None if cache_dir is None else os.fsencode(cache_dir),
+                                             None if rank is None or n == 0 else _ptr(rank), _ptr(best), _ptr(best_ani))
+        if st != GG_OK:
+            raise self._err(st)
+        return best[:nq], best_ani[:nq]
 
     def sketch_files(self, paths, cache_dir=None):
         """finch sketch_files (src/finch.rs:47) for files -> (sketches [n, s] u64
@@ -2277,6 +2420,61 @@ class Collection:
         except GalahGpuError as e:
             raise RuntimeError("Failed to cluster genomes: %s" % e) from e
         return clusters_from_reps(rep_of)
+
+    def query(self, paths, min_ani=None):
+        """The genomes of the collection each file is close to, without adding
+        it: per path a list of (index into .paths, np.float32 ani), ANI
+        descending, then index.  min_ani (a fraction): None, the
+        preclusterer's.  A path already in the collection is allowed (it finds
+        itself at ANI 1.0).  The collection is not changed."""
+        qp = [os.fspath(p) for p in paths]
+        thr = float(np.float32(self._pre.min_ani if min_ani is None else min_ani))
+        try:
+            pairs, ani = self._ctx.collection_query_files(self._h, qp, thr, cache_dir=self._pre.sketch_cache_dir)
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+        n = len(self._paths)
+        out = [[] for _ in qp]
+        for p, a in zip(pairs, ani):
+            out[int(p["j"]) - n].append((int(p["i"]), np.float32(a)))
+        for hits in out:
+            hits.sort(key=lambda h: (-float(h[1]), h[0]))
+        return out
+
+    def classify(self, paths, clusterer, order=None):
+        """What galah would decide for each file appended last to the
+        clustering of the collection in `order` (as cluster takes it), each
+        decided alone: None when the genome would be a new representative,
+        else (index into .paths of its representative, np.float32 ani).  The
+        collection is not changed."""
+        clusterer.initialise()
+        pre_name, clu_name = self._pre.method_name(), clusterer.method_name()
+        if not (pre_name == clu_name == "finch"):
+            raise NotImplementedError("galah_amd.Collection.classify: only finch + finch runs here, not %s + %s"
+                                      % (pre_name, clu_name))
+        n = len(self._paths)
+        if order is not None:
+            order = np.asarray(order, dtype=np.int64).reshape(-1)
+            if len(order) != n or (n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n)):
+                raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
+        threshold = np.float32(clusterer.get_ani_threshold())
+        qp = [os.fspath(p) for p in paths]
+        try:
+            rep_of = self._ctx.collection_cluster(self._h, float(threshold), order)
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to cluster genomes: %s" % e) from e
+        # rank[row] = the representative's position in the order; other rows are no candidates
+        rows = np.arange(n, dtype=np.int64) if order is None else order
+        rank = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        reps = np.nonzero(rep_of == np.arange(n, dtype=np.uint32))[0]
+        rank[rows[reps]] = reps.astype(np.uint32)
+        try:
+            best, best_ani = self._ctx.collection_classify_files(self._h, qp, rank,
+                                                                 cache_dir=self._pre.sketch_cache_dir)
+        except GalahGpuError as e:
+            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+        return [None if int(b["i"]) == 0xFFFFFFFF or not np.float32(a) >= threshold else (int(b["i"]), np.float32(a))
+                for b, a in zip(best, best_ani)]
 
     def state(self):
         """A PreclusterState of the collection (save / load as ever)."""

@@ -24,20 +24,6 @@
 
 using namespace gg;
 
-struct gg_collection {
-  gg_ctx* ctx = nullptr;  // as given to create / load
-  float min_ani = 0.0f;
-  uint32_t n = 0, row_cap = 0;
-  uint64_t n_pairs = 0;
-  uint64_t* sk = nullptr;    // [row_cap x s]
-  uint32_t* lens = nullptr;  // [row_cap]
-  gg_pair* pairs[2] = {nullptr, nullptr};
-  float* ani[2] = {nullptr, nullptr};
-  uint64_t pair_cap[2] = {0, 0};
-  int cur = 0;  // the buffer that holds the list
-  uint32_t grows = 0, rows_moved = 0;
-};
-
 namespace {
 
 constexpr uint64_t kBounceBytes = 64ull << 20;

@@ -189,6 +189,22 @@ struct gg_ctx {
   double phase_ms[GG_PHASE_COUNT] = {0};
 };
 
+// A collection resident on the device (collection.cpp owns and changes it;
+// query.cpp reads it).
+struct gg_collection {
+  gg_ctx* ctx = nullptr;  // as given to create / load
+  float min_ani = 0.0f;
+  uint32_t n = 0, row_cap = 0;
+  uint64_t n_pairs = 0;
+  uint64_t* sk = nullptr;    // [row_cap x s]
+  uint32_t* lens = nullptr;  // [row_cap]
+  gg_pair* pairs[2] = {nullptr, nullptr};
+  float* ani[2] = {nullptr, nullptr};
+  uint64_t pair_cap[2] = {0, 0};
+  int cur = 0;  // the buffer that holds the list
+  uint32_t grows = 0, rows_moved = 0;
+};
+
 namespace gg {
 
 // The member that single-device entry points use on a multi-device context.
@@ -471,6 +487,27 @@ gg_status inflate_batch(gg_ctx* m, const uint8_t* h_in, uint64_t in_bytes, const
 gg_status parse_raw_batch(gg_ctx* m, const uint8_t* d_text, const std::vector<uint64_t>& foff, uint32_t** d_words,
                           uint64_t* n_words, std::vector<gg_run>& runs,
                           std::vector<gg_genome_stats>* stats = nullptr);
+
+// The query of resident rows (query.hip, by query_core.hpp):
+// the passing cells (row i, query q) as gg_pair{i, n + q, common, total}
+// appended to d_out by gg_pairs_device's output contract.  n, nq >= 1 and
+// n + nq < 2^31: the caller's.
+//   query_append_device       a table of every batch of at most `batch`
+//     queries (clipped to query_core.hpp's), the rows streamed against it;
+//     d_cmin / d_sufmin: pairs_tables' with sufmin[0] != 0.  Synchronises st
+//     once per batch (the batch's entry count sizes its sort and table).
+//   query_rect_append_device  every cell, through the named-pair kernel
+//     (min_ani <= 0: all pass).  Asynchronous.
+gg_status query_append_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n, const uint64_t* d_q_sk,
+                              const uint32_t* d_q_lens, uint32_t nq, uint32_t batch, const uint32_t* d_cmin,
+                              const uint32_t* d_sufmin, gg_pair* d_out, uint64_t cap, uint64_t* d_count, hipStream_t st);
+gg_status query_rect_append_device(gg_ctx* c, const uint64_t* d_sk, const uint32_t* d_lens, uint32_t n,
+                                   const uint64_t* d_q_sk, const uint32_t* d_q_lens, uint32_t nq, gg_pair* d_out,
+                                   uint64_t cap, uint64_t* d_count, hipStream_t st);
+// best[q] / best_ani[q] of nq queries from their hits in any order (d_rank
+// [n] or null); pairs that name no row < n or no query are skipped.  Asynchronous.
+gg_status query_best_device(gg_ctx* c, uint32_t n, uint32_t nq, const gg_pair* d_pairs, const float* d_ani,
+                            uint64_t n_pairs, const uint32_t* d_rank, gg_pair* d_best, float* d_best_ani, hipStream_t st);
 
 // A timing event of c (a spare one, else a new one; nullptr on failure).
 hipEvent_t take_event(gg_ctx* c);

@@ -511,6 +511,35 @@ inline std::vector<gg_pair> pairs_matrix(const std::vector<uint64_t>& sketches, 
   return out;
 }
 
+// The hits of queries that are not to be added (gg_query_rows): every cell
+// (row i, query q) at or above min_ani (a fraction) as gg_pair{i, lens.size()
+// + q, common, total}, sorted by (i, j), with their f32 ANI in *ani (may be
+// null).  sketches is [lens.size() x sketch_size], q_sketches [q_lens.size() x
+// sketch_size], rows ascending.
+inline std::vector<gg_pair> query_rows(const std::vector<uint64_t>& sketches, const std::vector<uint32_t>& lens,
+                                       const std::vector<uint64_t>& q_sketches, const std::vector<uint32_t>& q_lens,
+                                       size_t sketch_size, float min_ani, std::vector<float>* ani = nullptr,
+                                       uint8_t kmer_length = 21) {
+  if (sketches.size() != lens.size() * sketch_size || q_sketches.size() != q_lens.size() * sketch_size)
+    throw std::invalid_argument("sketches must be [n x sketch_size]");
+  gg_status st = GG_OK;
+  gg_ctx* ctx = gg_create_multi(kmer_length, (uint32_t)sketch_size, 0, nullptr, 0, &st);
+  if (!ctx) throw std::runtime_error(gg_thread_last_error());
+  gg_pair* p = nullptr;
+  float* a = nullptr;
+  uint64_t n = 0;
+  st = gg_query_rows(ctx, sketches.data(), lens.data(), (uint32_t)lens.size(), q_sketches.data(), q_lens.data(),
+                     (uint32_t)q_lens.size(), min_ani, &p, &a, &n);
+  const std::string msg = st != GG_OK ? gg_last_error(ctx) : "";
+  gg_destroy(ctx);
+  if (st != GG_OK) throw std::runtime_error(msg);
+  std::vector<gg_pair> out(p, p + n);
+  if (ani) ani->assign(a, a + n);
+  gg_free(p);
+  gg_free(a);
+  return out;
+}
+
 // The finch ANI table of every precluster of the genomes
 // (gg_precluster_matrices_files): the files sketched once, the preclusters at
 // precluster_ani (a fraction) and each one's dense matrix in one grouped call

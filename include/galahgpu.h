@@ -874,6 +874,77 @@ gg_status gg_collection_rows(gg_collection* collection, uint64_t* sketches, uint
 gg_status gg_collection_view(gg_collection* collection, const uint64_t** d_sketches, const uint32_t** d_lens,
                              const gg_pair** d_pairs, const float** d_ani);
 
+/* ---- the query: hits and nearest representative ---------- */
+/* Rows 0 .. n-1 against queries 0 .. nq-1 of the same k, sketch size and seed
+ * that are NOT to be added: every cell (row i, query q) that passes the pair
+ * test at the call's own min_ani (any f32; NaN is refused), as
+ * gg_pair{ i, j = n + q, common, total } with finch's merge-to-first-exhaustion
+ * values.  The host-returning forms give the pairs sorted by (i, j) and their
+ * f32 ANI (the ANI function of the host arithmetic below, bit for bit), so that
+ *
+ *   query(rows, queries, min_ani)
+ *     == [p for p in border(rows ++ queries, n_old = n, min_ani) if p.i < n]
+ *
+ * in content and order.  No query x query cell is evaluated.  min_ani <= 0:
+ * every cell passes, an empty row against an empty query as (0, 0), ANI 0.
+ * n == 0 or nq == 0: an empty result.  Limits, checked before any work with
+ * GG_ERR_INVALID_ARG: n + nq < 2^31, and fewer than 2^31 passing pairs in the
+ * forms that return to the host.  A multi-device context acts on its first
+ * member, as the border does.  A query is not a pair-kernel call over tiles:
+ * the pair-path, paths-taken and fallback counters do not count it.  Timing:
+ * the table build under GG_KERNEL_PAIRS_INDEX (work: entries), the stream
+ * kernel under GG_KERNEL_PAIRS (work: n x the batch's queries), the best hit
+ * under GG_KERNEL_CLUSTER (work: hits).
+ *
+ * _host: no device, no context, n x nq merges.  _rows: host arrays (lens <=
+ * sketch_size is checked).  _rows_device: device arrays, nothing is checked;
+ * the pairs are appended unsorted by the device pair call's output contract
+ * (entries past out_cap are dropped but counted, *d_count is added to, a NULL
+ * d_out with out_cap 0 only counts); the call synchronises `stream`. */
+gg_status gg_query_host(const uint64_t* sketches, const uint32_t* lens, uint32_t n, const uint64_t* q_sketches,
+                        const uint32_t* q_lens, uint32_t nq, uint32_t sketch_size, int kmer_length, float min_ani,
+                        gg_pair** out, uint64_t* n_out);
+gg_status gg_query_rows(gg_ctx* ctx, const uint64_t* sketches, const uint32_t* lens, uint32_t n,
+                        const uint64_t* q_sketches, const uint32_t* q_lens, uint32_t nq, float min_ani, gg_pair** pairs,
+                        float** ani, uint64_t* n_out);
+gg_status gg_query_rows_device(gg_ctx* ctx, const uint64_t* d_sketches, const uint32_t* d_lens, uint32_t n,
+                               const uint64_t* d_q_sketches, const uint32_t* d_q_lens, uint32_t nq, float min_ani,
+                               gg_pair* d_out, uint64_t out_cap, uint64_t* d_count, void* stream);
+/* The nearest candidate of every query from its hits (any order), their f32
+ * ANI and rank [n] u32 (0xFFFFFFFF: the row is no candidate; NULL: every row
+ * is one, rank = row): the candidate with the largest f32 ANI, ties to the
+ * smallest rank -- galah's membership rule (src/clusterer.rs:376-399).
+ * best[q] is the winning pair (i = 0xFFFFFFFF, j = n + q when no candidate
+ * hit), best_ani[q] its ANI (0 then).  With the hits at a collection's min_ani
+ * and rank = each representative's position in the clustering order, query q
+ * appended last in that order would be a member of best[q].i iff best_ani[q]
+ * >= cluster_ani (f32 against f32), else a new representative.  _host checks
+ * index ranges, NaN ANI and that the candidates' ranks are distinct; _device
+ * checks nothing and skips a pair with i >= n or j - n >= nq. */
+gg_status gg_query_best_host(uint32_t n, uint32_t nq, const gg_pair* pairs, const float* ani, uint64_t n_pairs,
+                             const uint32_t* rank, gg_pair* best, float* best_ani);
+gg_status gg_query_best_device(gg_ctx* ctx, uint32_t n, uint32_t nq, const gg_pair* d_pairs, const float* d_ani,
+                               uint64_t n_pairs, const uint32_t* d_rank, gg_pair* d_best, float* d_best_ani,
+                               void* stream);
+/* A collection queried: it is never changed (rows, pairs, ANI, n, capacities,
+ * grows and the view pointers stay as they were).  _rows: host queries.
+ * _files: the files are read and sketched exactly as the collection's add
+ * sketches them (cache_dir, GG_ERR_IO / GG_ERR_PARSE of the lowest failing
+ * index); q_hashes [nq x sketch_size] and q_lens [nq] (each may be NULL)
+ * receive the sketches -- on a one-device context the hashes visit the host
+ * only then.  The classify forms run at the collection's min_ani, keep the hit
+ * list on the device and bring down best / best_ani [nq] only; rank [n] or
+ * NULL as above (distinct candidate ranks are checked). */
+gg_status gg_collection_query_rows(gg_collection* collection, const uint64_t* q_sketches, const uint32_t* q_lens,
+                                   uint32_t nq, float min_ani, gg_pair** pairs, float** ani, uint64_t* n_out);
+gg_status gg_collection_query_files(gg_collection* collection, const char* const* paths, uint32_t nq,
+                                    const char* cache_dir, float min_ani, uint64_t* q_hashes, uint32_t* q_lens,
+                                    gg_pair** pairs, float** ani, uint64_t* n_out);
+gg_status gg_collection_classify_rows(gg_collection* collection, const uint64_t* q_sketches, const uint32_t* q_lens,
+                                      uint32_t nq, const uint32_t* rank, gg_pair* best, float* best_ani);
+gg_status gg_collection_classify_files(gg_collection* collection, const char* const* paths, uint32_t nq,
+                                       const char* cache_dir, const uint32_t* rank, gg_pair* best, float* best_ani);
+
 /* ---- host arithmetic shared with the caller ---------------------------- */
 /* src/finch.rs:56-64: 1 - finch mash_distance, f64, Rust NaN semantics */
 double gg_ani_f64(uint32_t common, uint32_t total, int kmer_length);

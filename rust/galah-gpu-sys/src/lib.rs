@@ -447,6 +447,33 @@ extern "C" {
     pub fn gg_collection_view(collection: *mut gg_collection, d_sketches: *mut *const u64, d_lens: *mut *const u32,
                               d_pairs: *mut *const gg_pair, d_ani: *mut *const f32) -> GgStatus;
 
+    // the query: hits and nearest representative of genomes that are not added
+    pub fn gg_query_host(sketches: *const u64, lens: *const u32, n: u32, q_sketches: *const u64, q_lens: *const u32,
+                         nq: u32, sketch_size: u32, kmer_length: c_int, min_ani: f32, out: *mut *mut gg_pair,
+                         n_out: *mut u64) -> GgStatus;
+    pub fn gg_query_rows(ctx: *mut gg_ctx, sketches: *const u64, lens: *const u32, n: u32, q_sketches: *const u64,
+                         q_lens: *const u32, nq: u32, min_ani: f32, pairs: *mut *mut gg_pair, ani: *mut *mut f32,
+                         n_out: *mut u64) -> GgStatus;
+    pub fn gg_query_rows_device(ctx: *mut gg_ctx, d_sketches: *const u64, d_lens: *const u32, n: u32,
+                                d_q_sketches: *const u64, d_q_lens: *const u32, nq: u32, min_ani: f32,
+                                d_out: *mut gg_pair, out_cap: u64, d_count: *mut u64, stream: *mut c_void) -> GgStatus;
+    pub fn gg_query_best_host(n: u32, nq: u32, pairs: *const gg_pair, ani: *const f32, n_pairs: u64, rank: *const u32,
+                              best: *mut gg_pair, best_ani: *mut f32) -> GgStatus;
+    pub fn gg_query_best_device(ctx: *mut gg_ctx, n: u32, nq: u32, d_pairs: *const gg_pair, d_ani: *const f32,
+                                n_pairs: u64, d_rank: *const u32, d_best: *mut gg_pair, d_best_ani: *mut f32,
+                                stream: *mut c_void) -> GgStatus;
+    pub fn gg_collection_query_rows(collection: *mut gg_collection, q_sketches: *const u64, q_lens: *const u32, nq: u32,
+                                    min_ani: f32, pairs: *mut *mut gg_pair, ani: *mut *mut f32, n_out: *mut u64)
+        -> GgStatus;
+    pub fn gg_collection_query_files(collection: *mut gg_collection, paths: *const *const c_char, nq: u32,
+                                     cache_dir: *const c_char, min_ani: f32, q_hashes: *mut u64, q_lens: *mut u32,
+                                     pairs: *mut *mut gg_pair, ani: *mut *mut f32, n_out: *mut u64) -> GgStatus;
+    pub fn gg_collection_classify_rows(collection: *mut gg_collection, q_sketches: *const u64, q_lens: *const u32,
+                                       nq: u32, rank: *const u32, best: *mut gg_pair, best_ani: *mut f32) -> GgStatus;
+    pub fn gg_collection_classify_files(collection: *mut gg_collection, paths: *const *const c_char, nq: u32,
+                                        cache_dir: *const c_char, rank: *const u32, best: *mut gg_pair,
+                                        best_ani: *mut f32) -> GgStatus;
+
     // host arithmetic
     pub fn gg_ani_f64(common: u32, total: u32, kmer_length: c_int) -> f64;
     pub fn gg_ani_f32(common: u32, total: u32, kmer_length: c_int) -> f32;
