@@ -19,7 +19,14 @@ inspected), but every compute call needs a gfx950 device and raises
 GalahGpuError otherwise.  The library must have been built in-tree
 (`make -C galah_amd/csrc` or __graft_entry__.build()); a missing library is
 an ImportError, never a silent substitute.
+
+Every wrapper goes through one call frame: _tcall /
+Context._call / Context._hcall turn a status into the exception of its error
+source; _paths_arg, _dir_arg and _rows_out make the arguments; _PairsOut and
+_take_array take what the library allocated.  This stays one file: the tests
+execute it a second time as a plain module over a second library.
 """
+import contextlib
 import ctypes
 import logging
 import os
@@ -127,6 +134,9 @@ if not os.path.exists(LIB_PATH):
 _L = ctypes.CDLL(LIB_PATH)
 _vp = ctypes.c_void_p
 _u32, _u64, _i32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+# the spellings the signature table repeats
+_f32, _f64, _str, _byref = ctypes.c_float, ctypes.c_double, ctypes.c_char_p, ctypes.byref
+_pvp, _pu32, _pu64, _pi32, _pstr = (ctypes.POINTER(t) for t in (_vp, _u32, _u64, _i32, _str))
 
 
 def _sig(name, res, args):
@@ -140,183 +150,150 @@ def _sig(name, res, args):
     f.argtypes = args
 
 
-_sig("gg_abi_version", _u32, [])
-_sig("gg_status_string", ctypes.c_char_p, [_i32])
-_sig("gg_last_error", ctypes.c_char_p, [_vp])
-_sig("gg_thread_last_error", ctypes.c_char_p, [])
-_sig("gg_create", _vp, [_i32, _u32, _u64, _i32, ctypes.POINTER(_i32)])
-_sig("gg_destroy", None, [_vp])
-_sig("gg_device", _i32, [_vp])
-_sig("gg_create_multi", _vp, [_i32, _u32, _u64, _vp, _u32, ctypes.POINTER(_i32)])
-_sig("gg_device_count", _u32, [_vp])
-_sig("gg_device_ctx", _vp, [_vp, _u32])
-_sig("gg_set_host_threads", _i32, [_vp, _i32])
-_sig("gg_phase_times", _i32, [_vp, _vp])
-_sig("gg_precluster_shards", _i32, [_vp, _vp, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                    ctypes.POINTER(_u64)])
-_sig("gg_pack_files", _i32, [ctypes.POINTER(ctypes.c_char_p), _u32, _i32, _i32, ctypes.POINTER(ctypes.POINTER(_Packed))])
-_sig("gg_pack_records", _i32, [ctypes.POINTER(_vp), _vp, _vp, _u64, _u32, _i32, ctypes.POINTER(ctypes.POINTER(_Packed))])
-_sig("gg_packed_free", None, [ctypes.POINTER(_Packed)])
-_sig("gg_sketch", _i32, [_vp, ctypes.POINTER(_Packed), _vp, _vp])
-_sig("gg_sketch_device", _i32, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _vp])
-_sig("gg_pair_tiles", _u64, [_u32])
-_sig("gg_pair_partition", None, [_u32, _u32, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64)])
-_sig("gg_pairs", _i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
-_sig("gg_pairs_device", _i32, [_vp, _vp, _vp, _u32, _u64, _u64, ctypes.c_float, _vp, _u64, _vp, _vp])
-_sig("gg_pairs_border", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
-_sig("gg_pairs_border_device", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, _vp, _u64, _vp, _vp])
-_sig("gg_pairs_border_host", _i32, [_vp, _vp, _u32, _u32, _u32, _i32, ctypes.c_float, ctypes.POINTER(_vp),
-                                    ctypes.POINTER(_u64)])
-_sig("gg_update_files", _i32, [_vp, _vp, _vp, _u32, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
-                               ctypes.c_char_p, _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                               ctypes.POINTER(_u64)])
-_sig("gg_precluster_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
-                                   ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
-_sig("gg_precluster_files_cached", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
-                                          ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                          ctypes.POINTER(_u64), ctypes.POINTER(_u32)])
-# gg_pair_sink: int (*)(void* user, const gg_pair* pairs, uint64_t n)
-PAIR_SINK = ctypes.CFUNCTYPE(_i32, _vp, _vp, _u64)
-_sig("gg_precluster_files_each", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_char_p,
-                                        PAIR_SINK, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                        ctypes.POINTER(_u64), ctypes.POINTER(_u32)])
-_sig("gg_sketch_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp,
-                               ctypes.POINTER(_u32)])
-_sig("gg_genome_stats_files", _i32, [ctypes.POINTER(ctypes.c_char_p), _u32, _i32, _vp])
-_sig("gg_sketch_files_stats", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp, _vp])
-_sig("gg_sketch_cache_load", _i32, [ctypes.c_char_p, ctypes.c_char_p, _i32, _u32, _u64, _vp,
-                                    ctypes.POINTER(_u32), ctypes.POINTER(_i32)])
-_sig("gg_sketch_cache_store", _i32, [ctypes.c_char_p, ctypes.c_char_p, _i32, _u32, _u64, _vp, _u32])
-_sig("gg_ani_f64", ctypes.c_double, [_u32, _u32, _i32])
-_sig("gg_ani_f32", ctypes.c_float, [_u32, _u32, _i32])
-_sig("gg_parse_percentage", _i32, [ctypes.c_float, ctypes.POINTER(ctypes.c_float)])
-_sig("gg_free", None, [_vp])
-_sig("gg_synth_clustered_device", _i32, [_vp, _u32, _u32, _u32, _u32, ctypes.c_float, _u64, _vp, _vp, _vp])
-_sig("gg_synth_mixed_lengths", _i32, [_u32, _u32, _u32, _u32, _u32, _u64, _vp])
-_sig("gg_synth_mixed_device", _i32, [_vp, _u32, _u32, _vp, _u32, ctypes.c_float, ctypes.c_double, _u64, _vp, _vp,
-                                     _u64, ctypes.POINTER(_u64), _vp])
-_sig("gg_partition_preclusters", _i32, [_u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32)])
-_sig("gg_precluster_pairs", _i32, [_u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp])
-_sig("gg_preclusters", _i32, [_vp, _u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32), _vp, _vp])
-_sig("gg_preclusters_device", _i32, [_vp, _u32, _vp, _u64, _vp, _vp, ctypes.POINTER(_u32), _vp, _vp, _vp])
-_sig("gg_cluster_pairs_host", _i32, [_u32, _vp, _vp, _u64, ctypes.c_float, _vp])
-_sig("gg_cluster_pairs", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float, _vp])
-_sig("gg_cluster_pairs_device", _i32, [_vp, _u32, _vp, _vp, _u64, ctypes.c_float, _vp, _vp])
-_sig("gg_clusters_from_reps", _i32, [_u32, _vp, _vp, _vp, ctypes.POINTER(_u32)])
-_sig("gg_cluster_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_float,
-                                ctypes.c_char_p, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
-
-
-class _ClusterSummary(ctypes.Structure):
-    _fields_ = [("n_pairs", ctypes.c_uint64), ("ani_rechecked", ctypes.c_uint64), ("n_preclusters", ctypes.c_uint32),
-                ("largest_precluster", ctypes.c_uint32), ("pair_passes", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32)]
+class _Summary(ctypes.Structure):
+    """A summary struct of counters: as_dict gives every field as an int (a `reserved` word is left out)."""
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
 
 
-_sig("gg_ani_f32_device", _i32, [_vp, _vp, _u64, _vp, _vp, ctypes.POINTER(_u64), _vp])
-_sig("gg_cluster_rows_device", _i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.c_float, _vp,
-                                      ctypes.POINTER(_ClusterSummary), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp])
-_sig("gg_cluster_files_resident", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_float,
-                                         ctypes.c_char_p, _vp, ctypes.POINTER(_ClusterSummary)])
+_sig("gg_abi_version", _u32, [])
+_sig("gg_status_string", _str, [_i32])
+_sig("gg_last_error", _str, [_vp])
+_sig("gg_thread_last_error", _str, [])
+_sig("gg_create", _vp, [_i32, _u32, _u64, _i32, _pi32])
+_sig("gg_destroy", None, [_vp])
+_sig("gg_device", _i32, [_vp])
+_sig("gg_create_multi", _vp, [_i32, _u32, _u64, _vp, _u32, _pi32])
+_sig("gg_device_count", _u32, [_vp])
+_sig("gg_device_ctx", _vp, [_vp, _u32])
+_sig("gg_set_host_threads", _i32, [_vp, _i32])
+_sig("gg_phase_times", _i32, [_vp, _vp])
+_sig("gg_precluster_shards", _i32, [_vp, _vp, _f32, _pvp, _pvp, _pu64])
+_sig("gg_pack_files", _i32, [_pstr, _u32, _i32, _i32, ctypes.POINTER(ctypes.POINTER(_Packed))])
+_sig("gg_pack_records", _i32, [_pvp, _vp, _vp, _u64, _u32, _i32, ctypes.POINTER(ctypes.POINTER(_Packed))])
+_sig("gg_packed_free", None, [ctypes.POINTER(_Packed)])
+_sig("gg_sketch", _i32, [_vp, ctypes.POINTER(_Packed), _vp, _vp])
+_sig("gg_sketch_device", _i32, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _vp])
+_sig("gg_pair_tiles", _u64, [_u32])
+_sig("gg_pair_partition", None, [_u32, _u32, _u32, _pu64, _pu64])
+_sig("gg_pairs", _i32, [_vp, _vp, _vp, _u32, _f32, _pvp, _pu64])
+_sig("gg_pairs_device", _i32, [_vp, _vp, _vp, _u32, _u64, _u64, _f32, _vp, _u64, _vp, _vp])
+_sig("gg_pairs_border", _i32, [_vp, _vp, _vp, _u32, _u32, _f32, _pvp, _pu64])
+_sig("gg_pairs_border_device", _i32, [_vp, _vp, _vp, _u32, _u32, _f32, _vp, _u64, _vp, _vp])
+_sig("gg_pairs_border_host", _i32, [_vp, _vp, _u32, _u32, _u32, _i32, _f32, _pvp, _pu64])
+_sig("gg_update_files", _i32, [_vp, _vp, _vp, _u32, _pstr, _u32, _f32, _str, _vp, _vp, _pvp, _pvp, _pu64])
+_sig("gg_precluster_files", _i32, [_vp, _pstr, _u32, _f32, _pvp, _pvp, _pu64])
+_sig("gg_precluster_files_cached", _i32, [_vp, _pstr, _u32, _f32, _str, _pvp, _pvp, _pu64, _pu32])
+# gg_pair_sink: int (*)(void* user, const gg_pair* pairs, uint64_t n)
+PAIR_SINK = ctypes.CFUNCTYPE(_i32, _vp, _vp, _u64)
+_sig("gg_precluster_files_each", _i32, [_vp, _pstr, _u32, _f32, _str, PAIR_SINK, _vp, _pvp, _pvp, _pu64, _pu32])
+_sig("gg_sketch_files", _i32, [_vp, _pstr, _u32, _str, _vp, _vp, _pu32])
+_sig("gg_genome_stats_files", _i32, [_pstr, _u32, _i32, _vp])
+_sig("gg_sketch_files_stats", _i32, [_vp, _pstr, _u32, _str, _vp, _vp, _vp])
+_sig("gg_sketch_cache_load", _i32, [_str, _str, _i32, _u32, _u64, _vp, _pu32, _pi32])
+_sig("gg_sketch_cache_store", _i32, [_str, _str, _i32, _u32, _u64, _vp, _u32])
+_sig("gg_ani_f64", _f64, [_u32, _u32, _i32])
+_sig("gg_ani_f32", _f32, [_u32, _u32, _i32])
+_sig("gg_parse_percentage", _i32, [_f32, ctypes.POINTER(_f32)])
+_sig("gg_free", None, [_vp])
+_sig("gg_synth_clustered_device", _i32, [_vp, _u32, _u32, _u32, _u32, _f32, _u64, _vp, _vp, _vp])
+_sig("gg_synth_mixed_lengths", _i32, [_u32, _u32, _u32, _u32, _u32, _u64, _vp])
+_sig("gg_synth_mixed_device", _i32, [_vp, _u32, _u32, _vp, _u32, _f32, _f64, _u64, _vp, _vp, _u64, _pu64, _vp])
+_sig("gg_partition_preclusters", _i32, [_u32, _vp, _u64, _vp, _vp, _pu32])
+_sig("gg_precluster_pairs", _i32, [_u32, _vp, _u64, _vp, _vp, _u32, _vp, _vp])
+_sig("gg_preclusters", _i32, [_vp, _u32, _vp, _u64, _vp, _vp, _pu32, _vp, _vp])
+_sig("gg_preclusters_device", _i32, [_vp, _u32, _vp, _u64, _vp, _vp, _pu32, _vp, _vp, _vp])
+_sig("gg_cluster_pairs_host", _i32, [_u32, _vp, _vp, _u64, _f32, _vp])
+_sig("gg_cluster_pairs", _i32, [_vp, _u32, _vp, _vp, _u64, _f32, _vp])
+_sig("gg_cluster_pairs_device", _i32, [_vp, _u32, _vp, _vp, _u64, _f32, _vp, _vp])
+_sig("gg_clusters_from_reps", _i32, [_u32, _vp, _vp, _vp, _pu32])
+_sig("gg_cluster_files", _i32, [_vp, _pstr, _u32, _f32, _f32, _str, _vp, _pvp, _pvp, _pu64])
+
+
+class _ClusterSummary(_Summary):
+    _fields_ = [("n_pairs", ctypes.c_uint64), ("ani_rechecked", ctypes.c_uint64), ("n_preclusters", ctypes.c_uint32),
+                ("largest_precluster", ctypes.c_uint32), ("pair_passes", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+_sig("gg_ani_f32_device", _i32, [_vp, _vp, _u64, _vp, _vp, _pu64, _vp])
+_sig("gg_cluster_rows_device", _i32, [_vp, _vp, _vp, _u32, _f32, _f32, _vp, ctypes.POINTER(_ClusterSummary), _pvp, _pvp,
+                                      _vp])
+_sig("gg_cluster_files_resident", _i32, [_vp, _pstr, _u32, _f32, _f32, _str, _vp, ctypes.POINTER(_ClusterSummary)])
 _sig("gg_ani_pairs_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _u64, _vp])
 _sig("gg_ani_pairs", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
 _sig("gg_ani_pairs_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp])
 
 
-class _MatrixSummary(ctypes.Structure):
+class _MatrixSummary(_Summary):
     _fields_ = [("n_entries", ctypes.c_uint64), ("n_columns", ctypes.c_uint64), ("column_entries", ctypes.c_uint64),
                 ("ani_rechecked", ctypes.c_uint64)]
 
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
-
+_pms = ctypes.POINTER(_MatrixSummary)
 _sig("gg_ani_matrix_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _u32, _vp, _vp, _vp])
-_sig("gg_ani_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, ctypes.POINTER(_MatrixSummary)])
-_sig("gg_ani_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, ctypes.POINTER(_MatrixSummary),
-                                    _vp])
-_sig("gg_ani_matrix_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp, _vp,
-                                   ctypes.POINTER(_MatrixSummary)])
+_sig("gg_ani_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _pms])
+_sig("gg_ani_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _pms, _vp])
+_sig("gg_ani_matrix_files", _i32, [_vp, _pstr, _u32, _str, _vp, _vp, _vp, _pms])
 _sig("gg_ani_matrix_group_cells", _i32, [_vp, _u32, _vp])
 _sig("gg_ani_matrix_groups_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _vp, _u32, _vp, _vp, _vp])
-_sig("gg_ani_matrix_groups", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp,
-                                    ctypes.POINTER(_MatrixSummary)])
-_sig("gg_ani_matrix_groups_device", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp,
-                                           ctypes.POINTER(_MatrixSummary), _vp])
-_sig("gg_precluster_matrices_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float, ctypes.c_char_p,
-                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u32),
-                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                            ctypes.POINTER(_vp), ctypes.POINTER(_MatrixSummary)])
+_sig("gg_ani_matrix_groups", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _pms])
+_sig("gg_ani_matrix_groups_device", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _pms, _vp])
+_sig("gg_precluster_matrices_files", _i32, [_vp, _pstr, _u32, _f32, _str, _pvp, _pvp, _pu32, _pvp, _pvp, _pvp, _pvp,
+                                            _pms])
 
 
-class _PairsMatrixSummary(ctypes.Structure):
+class _PairsMatrixSummary(_Summary):
     _fields_ = [("n_entries", ctypes.c_uint64), ("n_columns", ctypes.c_uint64), ("column_entries", ctypes.c_uint64),
                 ("n_pairs", ctypes.c_uint64), ("chunk_rounds", ctypes.c_uint64), ("index_reads", ctypes.c_uint64),
                 ("path", ctypes.c_uint32), ("pair_passes", ctypes.c_uint32)]
 
     def as_dict(self):
-        d = {f: int(getattr(self, f)) for f, _ in self._fields_}
+        d = super().as_dict()
         d["path"] = PAIRS_PATHS[d["path"]]
         return d
 
 
 PAIRS_PATHS = ("default", "matrix", "auto")  # GG_PAIRS_PATH_*
-_sig("gg_pairs_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, ctypes.c_float, _vp, _u64, _vp,
-                                      ctypes.POINTER(_PairsMatrixSummary), _vp])
-_sig("gg_pairs_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp),
-                               ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
-_sig("gg_pairs_border_matrix_device", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, _vp, _u64, _vp,
-                                              ctypes.POINTER(_PairsMatrixSummary), _vp])
-_sig("gg_pairs_border_matrix", _i32, [_vp, _vp, _vp, _u32, _u32, ctypes.c_float, ctypes.POINTER(_vp),
-                                       ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
+_ppms = ctypes.POINTER(_PairsMatrixSummary)
+_sig("gg_pairs_matrix_device", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _f32, _vp, _u64, _vp, _ppms, _vp])
+_sig("gg_pairs_matrix", _i32, [_vp, _vp, _vp, _u32, _vp, _u32, _f32, _pvp, _pu64, _ppms])
+_sig("gg_pairs_border_matrix_device", _i32, [_vp, _vp, _vp, _u32, _u32, _f32, _vp, _u64, _vp, _ppms, _vp])
+_sig("gg_pairs_border_matrix", _i32, [_vp, _vp, _vp, _u32, _u32, _f32, _pvp, _pu64, _ppms])
 _sig("gg_set_pairs_path", _i32, [_vp, _i32])
 _sig("gg_pairs_path", _i32, [_vp])
 _sig("gg_pairs_paths_taken", _i32, [_vp, _vp])
-_sig("gg_precluster_files_resident", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_float,
-                                            ctypes.c_char_p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                            ctypes.POINTER(_u64), ctypes.POINTER(_PairsMatrixSummary)])
+_sig("gg_precluster_files_resident", _i32, [_vp, _pstr, _u32, _f32, _str, _pvp, _pvp, _pu64, _ppms])
 
 
-class _CollectionInfo(ctypes.Structure):
+class _CollectionInfo(_Summary):
     _fields_ = [("n_pairs", ctypes.c_uint64), ("pair_capacity", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
                 ("n_rows", ctypes.c_uint32), ("row_capacity", ctypes.c_uint32), ("grows", ctypes.c_uint32),
                 ("rows_moved", ctypes.c_uint32)]
 
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
-
-_sig("gg_collection_create", _i32, [_vp, ctypes.c_float, _u32, _u64, ctypes.POINTER(_vp)])
+_sig("gg_collection_create", _i32, [_vp, _f32, _u32, _u64, _pvp])
 _sig("gg_collection_destroy", None, [_vp])
-_sig("gg_collection_stat", _i32, [_vp, ctypes.POINTER(_CollectionInfo), ctypes.POINTER(ctypes.c_float)])
-_sig("gg_collection_load", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, ctypes.c_float, ctypes.POINTER(_vp)])
-_sig("gg_collection_add_rows", _i32, [_vp, _vp, _vp, _u32, ctypes.POINTER(_u64)])
-_sig("gg_collection_add_rows_device", _i32, [_vp, _vp, _vp, _u32, ctypes.POINTER(_u64), _vp])
-_sig("gg_collection_add_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p,
-                                       ctypes.POINTER(_u64)])
+_sig("gg_collection_stat", _i32, [_vp, ctypes.POINTER(_CollectionInfo), ctypes.POINTER(_f32)])
+_sig("gg_collection_load", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, _f32, _pvp])
+_sig("gg_collection_add_rows", _i32, [_vp, _vp, _vp, _u32, _pu64])
+_sig("gg_collection_add_rows_device", _i32, [_vp, _vp, _vp, _u32, _pu64, _vp])
+_sig("gg_collection_add_files", _i32, [_vp, _pstr, _u32, _str, _pu64])
 _sig("gg_collection_remove", _i32, [_vp, _vp, _u32, _vp])
-_sig("gg_collection_cluster", _i32, [_vp, _vp, ctypes.c_float, _vp])
-_sig("gg_collection_pairs", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_collection_cluster", _i32, [_vp, _vp, _f32, _vp])
+_sig("gg_collection_pairs", _i32, [_vp, _pvp, _pvp, _pu64])
 _sig("gg_collection_rows", _i32, [_vp, _vp, _vp])
-_sig("gg_collection_view", _i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                  ctypes.POINTER(_vp)])
-_sig("gg_query_host", _i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, ctypes.c_int, ctypes.c_float, ctypes.POINTER(_vp),
-                             ctypes.POINTER(_u64)])
-_sig("gg_query_rows", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp),
-                             ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
-_sig("gg_query_rows_device", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, ctypes.c_float, _vp, _u64, _vp, _vp])
+_sig("gg_collection_view", _i32, [_vp, _pvp, _pvp, _pvp, _pvp])
+_sig("gg_query_host", _i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _i32, _f32, _pvp, _pu64])
+_sig("gg_query_rows", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _f32, _pvp, _pvp, _pu64])
+_sig("gg_query_rows_device", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _f32, _vp, _u64, _vp, _vp])
 _sig("gg_query_best_host", _i32, [_u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp])
 _sig("gg_query_best_device", _i32, [_vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp])
-_sig("gg_collection_query_rows", _i32, [_vp, _vp, _vp, _u32, ctypes.c_float, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                        ctypes.POINTER(_u64)])
-_sig("gg_collection_query_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, ctypes.c_float,
-                                         _vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)])
+_sig("gg_collection_query_rows", _i32, [_vp, _vp, _vp, _u32, _f32, _pvp, _pvp, _pu64])
+_sig("gg_collection_query_files", _i32, [_vp, _pstr, _u32, _str, _f32, _vp, _vp, _pvp, _pvp, _pu64])
 _sig("gg_collection_classify_rows", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp])
-_sig("gg_collection_classify_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, ctypes.c_char_p, _vp, _vp,
-                                            _vp])
+_sig("gg_collection_classify_files", _i32, [_vp, _pstr, _u32, _str, _vp, _vp, _vp])
 
 
 class _Validation(ctypes.Structure):
@@ -324,11 +301,10 @@ class _Validation(ctypes.Structure):
                 ("rep_bad", ctypes.c_uint64)]
 
 
-_VOUT = [ctypes.POINTER(_Validation), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64)]
-_sig("gg_validate_clusters_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _vp, _u32, ctypes.c_float] + _VOUT)
-_sig("gg_validate_clusters", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, ctypes.c_float] + _VOUT)
-_sig("gg_validate_files", _i32, [_vp, ctypes.POINTER(ctypes.c_char_p), _u32, _vp, _vp, _u32, ctypes.c_float,
-                                 ctypes.c_char_p] + _VOUT)
+_VOUT = [ctypes.POINTER(_Validation), _pvp, _pvp, _pu64]
+_sig("gg_validate_clusters_host", _i32, [_vp, _vp, _u32, _u32, _i32, _vp, _vp, _u32, _f32] + _VOUT)
+_sig("gg_validate_clusters", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _f32] + _VOUT)
+_sig("gg_validate_files", _i32, [_vp, _pstr, _u32, _vp, _vp, _u32, _f32, _str] + _VOUT)
 
 
 class _KStats(ctypes.Structure):
@@ -339,7 +315,7 @@ _sig("gg_timing_enable", _i32, [_vp, _i32])
 _sig("gg_pair_paths", _i32, [_vp, _vp])
 _sig("gg_fallbacks", _i32, [_vp, _vp])
 _sig("gg_peer_links", _i32, [_vp, _vp])
-_sig("gg_info_line", _i32, [_vp, ctypes.c_char_p, ctypes.c_size_t])
+_sig("gg_info_line", _i32, [_vp, _str, ctypes.c_size_t])
 FALLBACKS = ("index_to_gate", "index_full_sort", "peer_staged", "sketch_retry", "inflate_host", "sketch_set")  # gg_fallbacks order
 _sig("gg_timing_read", _i32, [_vp, _i32, ctypes.POINTER(_KStats)])
 KERNEL_SKETCH, KERNEL_FINALIZE, KERNEL_PAIRS, KERNEL_PAIRS_INDEX = 0, 1, 2, 3
@@ -367,6 +343,79 @@ def _thread_err(st):
     return GalahGpuError(st, _L.gg_thread_last_error().decode(errors="replace"))
 
 
+# ---------------------------------------------------------------------------
+# The call frame
+# ---------------------------------------------------------------------------
+def _tcall(fn, *args):
+    """fn(*args) of an entry point that reports on the calling thread (the
+    host forms, and gg_collection_stat / gg_collection_view)."""
+    st = fn(*args)
+    if st != GG_OK:
+        raise _thread_err(st)
+
+
+def _paths_arg(paths):
+    """(char* array, n) of a list of paths; the array has one entry at least."""
+    n = len(paths)
+    return (_str * max(n, 1))(*[os.fsencode(p) for p in paths]), n
+
+
+def _dir_arg(cache_dir):
+    """A sketch cache directory as the library takes it: None is NULL, "" is passed on."""
+    return None if cache_dir is None else os.fsencode(cache_dir)
+
+
+def _rows_out(n, s):
+    """Row outputs for the library to fill -> (sketches pointer, lens pointer,
+    sketches [n, s] u64, lens [n] u32): allocated for one row at least, the
+    arrays returned are the first n rows of what the pointers name."""
+    out, lens = np.zeros((max(n, 1), s), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+    return _ptr(out), _ptr(lens), out[:n], lens[:n]
+
+
+def _best_out(nq):
+    """The outputs of a best-candidate call, as _rows_out -> (best pointer, ani pointer, best [nq], best_ani [nq])."""
+    best, best_ani = np.zeros(max(nq, 1), dtype=PAIR_DTYPE), np.zeros(max(nq, 1), dtype=np.float32)
+    return _ptr(best), _ptr(best_ani), best[:nq], best_ani[:nq]
+
+
+def _take_array(ptr, count, dtype):
+    """An array the library allocated, as a fresh numpy array; the library's is released."""
+    if count:
+        # one memmove into a fresh array (a ctypes array type per call, or
+        # np.ctypeslib.as_array, cost ~0.1-0.25 ms at C3's 15k pairs)
+        out = np.empty(count, dtype=dtype)
+        ctypes.memmove(out.ctypes.data, ptr.value, count * out.itemsize)
+    else:
+        out = np.zeros(0, dtype=dtype)
+    _L.gg_free(ptr)
+    return out
+
+
+def _take_pairs(ptr, n):
+    return _take_array(ptr, n, PAIR_DTYPE)
+
+
+def _take_pairs_ani(pp, ap, n):
+    ani = _take_array(ap, n, np.float32)
+    return _take_pairs(pp, n), ani
+
+
+class _PairsOut:
+    """The (gg_pair*, float*, uint64_t) a call returns its pairs in (without
+    ani: the pairs and their count alone): .refs are the arguments, take()
+    gives (pairs, ani f32), or the pairs, and releases the library's arrays."""
+
+    def __init__(self, ani=True):
+        self.pp, self.ap, self.cnt = _vp(), (_vp() if ani else None), _u64()
+        self.refs = tuple(_byref(x) for x in (self.pp, self.ap, self.cnt) if x is not None)
+
+    def take(self):
+        if self.ap is None:
+            return _take_pairs(self.pp, self.cnt.value)
+        return _take_pairs_ani(self.pp, self.ap, self.cnt.value)
+
+
 def abi_version():
     return _L.gg_abi_version()
 
@@ -384,9 +433,9 @@ def ani_f32(common, total, k=21):
 def parse_percentage(value):
     """CAP:1160-1182 for --precluster-ani: [1,100] -> /100 in f32,
     [0,1) kept, anything else is an error."""
-    out = ctypes.c_float()
-    st = _L.gg_parse_percentage(ctypes.c_float(value), ctypes.byref(out))
-    if st != GG_OK:
+    out = _f32()
+    st = _L.gg_parse_percentage(_f32(value), _byref(out))
+    if st != GG_OK:  # (its own class and text: the reference's message, no status suffix)
         raise ValueError(_L.gg_thread_last_error().decode())
     return np.float32(out.value)
 
@@ -397,7 +446,7 @@ def pair_tiles(n):
 
 def pair_partition(n, parts, part):
     b, e = _u64(), _u64()
-    _L.gg_pair_partition(n, parts, part, ctypes.byref(b), ctypes.byref(e))
+    _L.gg_pair_partition(n, parts, part, _byref(b), _byref(e))
     return b.value, e.value
 
 
@@ -417,9 +466,7 @@ def _as_pairs(pairs):
 def synth_mixed_lengths(n_genomes, min_len, max_len, cluster_size, seed, first_genome=0):
     """Config C5 genome lengths: log-uniform in [min_len, max_len] per cluster."""
     lens = np.zeros(max(n_genomes, 1), np.uint32)
-    st = _L.gg_synth_mixed_lengths(first_genome, n_genomes, min_len, max_len, cluster_size, seed, _ptr(lens))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_synth_mixed_lengths, first_genome, n_genomes, min_len, max_len, cluster_size, seed, _ptr(lens))
     return lens[:n_genomes]
 
 
@@ -432,9 +479,7 @@ def partition_preclusters(n_genomes, pairs):
     members = np.zeros(max(n_genomes, 1), np.uint32)
     offsets = np.zeros(n_genomes + 1, np.uint32)
     ns = _u32()
-    st = _L.gg_partition_preclusters(n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), ctypes.byref(ns))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_partition_preclusters, n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), _byref(ns))
     return members[:n_genomes], offsets[:ns.value + 1].copy()
 
 
@@ -448,10 +493,7 @@ def precluster_pairs(n_genomes, pairs, members, offsets):
     ns = len(offsets) - 1
     out = np.zeros(max(len(p), 1), LOCAL_PAIR_DTYPE)
     poff = np.zeros(ns + 1, np.uint64)
-    st = _L.gg_precluster_pairs(n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), ns, _ptr(out),
-                                _ptr(poff))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_precluster_pairs, n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), ns, _ptr(out), _ptr(poff))
     return out[:len(p)], poff
 
 
@@ -484,9 +526,7 @@ def cluster_pairs_host(n_genomes, pairs, ani, cluster_ani):
     Host C++ (gg_cluster_pairs_host), linear in the pairs."""
     p, a = _pairs_ani_arg(pairs, ani)
     rep_of = np.zeros(max(n_genomes, 1), np.uint32)
-    st = _L.gg_cluster_pairs_host(n_genomes, _ptr(p), _ptr(a), len(p), ctypes.c_float(cluster_ani), _ptr(rep_of))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_cluster_pairs_host, n_genomes, _ptr(p), _ptr(a), len(p), _f32(cluster_ani), _ptr(rep_of))
     return rep_of[:n_genomes]
 
 
@@ -498,9 +538,7 @@ def clusters_from_reps(rep_of):
     members = np.zeros(max(n, 1), np.uint32)
     offsets = np.zeros(n + 1, np.uint32)
     nc = _u32()
-    st = _L.gg_clusters_from_reps(n, _ptr(rep_of), _ptr(members), _ptr(offsets), ctypes.byref(nc))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_clusters_from_reps, n, _ptr(rep_of), _ptr(members), _ptr(offsets), _byref(nc))
     return [members[offsets[c]:offsets[c + 1]].tolist() for c in range(nc.value)]
 
 
@@ -570,17 +608,6 @@ class Validation:
                 % (self.member_pairs, self.member_bad, self.rep_pairs, self.rep_bad))
 
 
-def _take_validation(summary, bp, ap, cnt):
-    n = cnt.value
-    if n:
-        ani = np.empty(n, np.float32)
-        ctypes.memmove(ani.ctypes.data, ap.value, n * 4)
-    else:
-        ani = np.zeros(0, np.float32)
-    _L.gg_free(ap)
-    return Validation(summary, _take_pairs(bp, n), ani)
-
-
 def ani_pairs_host(sketches, lens, pairs, k=21):
     """finch's merge counts and the stored f32 ANI of the pairs named
     (src/lib.rs:29-37 calculate_ani for a whole list; gg_ani_pairs_host, no
@@ -589,9 +616,7 @@ def ani_pairs_host(sketches, lens, pairs, k=21):
     sk, ln, n, s = _rows_arg(sketches, lens)
     p = _pair_list_arg(pairs)
     ani = np.zeros(max(len(p), 1), np.float32)
-    st = _L.gg_ani_pairs_host(_ptr(sk), _ptr(ln), n, s, k, _ptr(p), len(p), _ptr(ani))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_ani_pairs_host, _ptr(sk), _ptr(ln), n, s, k, _ptr(p), len(p), _ptr(ani))
     return p, ani[:len(p)]
 
 
@@ -617,9 +642,7 @@ def ani_matrix_host(sketches, lens, rows=None, k=21):
     sk, ln, n, s = _rows_arg(sketches, lens)
     r, rp, m = _matrix_rows_arg(rows, n)
     common, total, ani = _matrix_out(m)
-    st = _L.gg_ani_matrix_host(_ptr(sk), _ptr(ln), n, s, k, rp, m, _ptr(common), _ptr(total), _ptr(ani))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_ani_matrix_host, _ptr(sk), _ptr(ln), n, s, k, rp, m, _ptr(common), _ptr(total), _ptr(ani))
     return common[:m, :m], total[:m, :m], ani[:m, :m]
 
 
@@ -646,9 +669,7 @@ def ani_matrix_group_cells(offsets):
     and for a call past the limits: 2^32 cells, 2^31 tile pairs)."""
     off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
     cells = np.zeros(len(off), np.uint64)
-    st = _L.gg_ani_matrix_group_cells(_ptr(off), len(off) - 1, _ptr(cells))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_ani_matrix_group_cells, _ptr(off), len(off) - 1, _ptr(cells))
     return cells
 
 
@@ -658,6 +679,16 @@ def ani_matrix_block(values, offsets, cell_offsets, g):
     return values[int(cell_offsets[g]):int(cell_offsets[g]) + m * m].reshape(m, m)
 
 
+def _groups_out(members, offsets):
+    """(members, offsets, n_groups, cell_offsets, common, total, ani) of a
+    grouped matrix call: the flat outputs hold one cell at least, z =
+    cell_offsets[-1] of them are the result."""
+    mem, off, ng = _groups_arg(members, offsets)
+    cells = ani_matrix_group_cells(off)
+    z = max(int(cells[-1]), 1)
+    return mem, off, ng, cells, np.zeros(z, np.uint32), np.zeros(z, np.uint32), np.zeros(z, np.float32)
+
+
 def ani_matrix_groups_host(sketches, lens, members, offsets=None, k=21):
     """ani_matrix_host for every group of a CSR at once (group g is
     members[offsets[g]:offsets[g + 1]]; or members a list of index lists):
@@ -665,14 +696,9 @@ def ani_matrix_groups_host(sketches, lens, members, offsets=None, k=21):
     total u32, ani f32, cell_offsets u64): flat arrays, block g row-major
     [m_g, m_g] at cell_offsets[g] (ani_matrix_block)."""
     sk, ln, n, s = _rows_arg(sketches, lens)
-    mem, off, ng = _groups_arg(members, offsets)
-    cells = ani_matrix_group_cells(off)
-    z = max(int(cells[-1]), 1)
-    common, total, ani = np.zeros(z, np.uint32), np.zeros(z, np.uint32), np.zeros(z, np.float32)
-    st = _L.gg_ani_matrix_groups_host(_ptr(sk), _ptr(ln), n, s, k, _ptr(mem), _ptr(off), ng, _ptr(common),
-                                      _ptr(total), _ptr(ani))
-    if st != GG_OK:
-        raise _thread_err(st)
+    mem, off, ng, cells, common, total, ani = _groups_out(members, offsets)
+    _tcall(_L.gg_ani_matrix_groups_host, _ptr(sk), _ptr(ln), n, s, k, _ptr(mem), _ptr(off), ng, _ptr(common),
+           _ptr(total), _ptr(ani))
     z = int(cells[-1])
     return common[:z], total[:z], ani[:z], cells
 
@@ -683,12 +709,9 @@ def pairs_border_host(sketches, lens, n_old, min_ani, k=21):
     that pairs(rows) == pairs(rows[:n_old]) + pairs_border(rows, n_old) as
     sets.  n_old == 0 gives every pair, n_old == n none."""
     sk, ln, n, s = _rows_arg(sketches, lens)
-    outp, cnt = _vp(), _u64()
-    st = _L.gg_pairs_border_host(_ptr(sk), _ptr(ln), n, int(n_old), s, int(k), ctypes.c_float(min_ani),
-                                 ctypes.byref(outp), ctypes.byref(cnt))
-    if st != GG_OK:
-        raise _thread_err(st)
-    return _take_pairs(outp, cnt.value)
+    out = _PairsOut(ani=False)
+    _tcall(_L.gg_pairs_border_host, _ptr(sk), _ptr(ln), n, int(n_old), s, int(k), _f32(min_ani), *out.refs)
+    return out.take()
 
 
 def query_host(sketches, lens, q_sketches, q_lens, min_ani, k=21):
@@ -699,21 +722,20 @@ def query_host(sketches, lens, q_sketches, q_lens, min_ani, k=21):
     s = int(widths[0]) if widths else 1  # (an empty side has no width of its own)
     sk, ln, n, _ = _rows_arg(sketches, lens, s)
     qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, s)
-    outp, cnt = _vp(), _u64()
-    st = _L.gg_query_host(_ptr(sk), _ptr(ln), n, _ptr(qs), _ptr(ql), nq, s, int(k), ctypes.c_float(min_ani),
-                          ctypes.byref(outp), ctypes.byref(cnt))
-    if st != GG_OK:
-        raise _thread_err(st)
-    return _take_pairs(outp, cnt.value)
+    out = _PairsOut(ani=False)
+    _tcall(_L.gg_query_host, _ptr(sk), _ptr(ln), n, _ptr(qs), _ptr(ql), nq, s, int(k), _f32(min_ani), *out.refs)
+    return out.take()
 
 
 def _rank_arg(rank, n):
+    """(rank [n] u32 or None, its pointer) of a query's candidate ranks; None,
+    or no rows: NULL, every row a candidate by its index."""
     if rank is None:
-        return None
+        return None, None
     rank = np.ascontiguousarray(rank, dtype=np.uint32).reshape(-1)
     if len(rank) != n:
         raise ValueError("one rank per row")
-    return rank
+    return rank, (_ptr(rank) if n else None)
 
 
 def query_best_host(n, nq, pairs, ani, rank=None):
@@ -721,14 +743,11 @@ def query_best_host(n, nq, pairs, ani, rank=None):
     i = 0xFFFFFFFF without a candidate hit; best_ani [nq] f32).  rank [n] u32,
     0xFFFFFFFF: no candidate; None: every row, by its index."""
     pa, an = _pairs_ani_arg(pairs, ani)
-    rank = _rank_arg(rank, n)
-    best = np.zeros(max(nq, 1), dtype=PAIR_DTYPE)
-    best_ani = np.zeros(max(nq, 1), dtype=np.float32)
-    st = _L.gg_query_best_host(int(n), int(nq), _ptr(pa) if len(pa) else None, _ptr(an) if len(an) else None, len(pa),
-                               None if rank is None or n == 0 else _ptr(rank), _ptr(best), _ptr(best_ani))
-    if st != GG_OK:
-        raise _thread_err(st)
-    return best[:nq], best_ani[:nq]
+    rank, rp = _rank_arg(rank, n)
+    bp, bap, best, best_ani = _best_out(nq)
+    _tcall(_L.gg_query_best_host, int(n), int(nq), _ptr(pa) if len(pa) else None, _ptr(an) if len(an) else None,
+           len(pa), rp, bp, bap)
+    return best, best_ani
 
 
 def validate_clusters_host(sketches, lens, clusters, ani, k=21):
@@ -737,13 +756,10 @@ def validate_clusters_host(sketches, lens, clusters, ani, k=21):
     first; ani the threshold as an f32 fraction -> Validation."""
     sk, ln, n, s = _rows_arg(sketches, lens)
     members, offsets, nc = _clusters_arg(clusters)
-    summary, bp, ap, cnt = _Validation(), _vp(), _vp(), _u64()
-    st = _L.gg_validate_clusters_host(_ptr(sk), _ptr(ln), n, s, k, _ptr(members), _ptr(offsets), nc,
-                                      ctypes.c_float(ani), ctypes.byref(summary), ctypes.byref(bp), ctypes.byref(ap),
-                                      ctypes.byref(cnt))
-    if st != GG_OK:
-        raise _thread_err(st)
-    return _take_validation(summary, bp, ap, cnt)
+    summary, bad = _Validation(), _PairsOut()
+    _tcall(_L.gg_validate_clusters_host, _ptr(sk), _ptr(ln), n, s, k, _ptr(members), _ptr(offsets), nc, _f32(ani),
+           _byref(summary), *bad.refs)
+    return Validation(summary, *bad.take())
 
 
 def read_clustering_file(path):
@@ -809,20 +825,16 @@ def sketch_cache_load(cache_dir, path, k=21, s=1000, seed=0):
     (ascending u64 array), or None when there is no valid entry.  Host only."""
     out = np.zeros(max(int(s), 1), dtype=np.uint64)
     n, hit = _u32(), _i32()
-    st = _L.gg_sketch_cache_load(os.fsencode(cache_dir), os.fsencode(path), int(k), int(s), int(seed),
-                                 _ptr(out), ctypes.byref(n), ctypes.byref(hit))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_sketch_cache_load, os.fsencode(cache_dir), os.fsencode(path), int(k), int(s), int(seed), _ptr(out),
+           _byref(n), _byref(hit))
     return out[:n.value].copy() if hit.value else None
 
 
 def sketch_cache_store(cache_dir, path, hashes, k=21, s=1000, seed=0):
     """Store the sketch of a genome file (strictly ascending, len <= s).  Host only."""
     h = np.ascontiguousarray(hashes, dtype=np.uint64)
-    st = _L.gg_sketch_cache_store(os.fsencode(cache_dir), os.fsencode(path), int(k), int(s), int(seed),
-                                  _ptr(h), len(h))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_sketch_cache_store, os.fsencode(cache_dir), os.fsencode(path), int(k), int(s), int(seed), _ptr(h),
+           len(h))
 
 
 # gg_genome_stats
@@ -866,12 +878,9 @@ def _stats_list(arr):
 def genome_stats(paths, threads=0):
     """src/genome_stats.rs:11 for every file, on `threads` host threads (0:
     the default of pack_files) -> a list of GenomeAssemblyStats.  Host only."""
-    n = len(paths)
-    arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+    arr, n = _paths_arg(paths)
     out = np.zeros(max(n, 1), dtype=STATS_DTYPE)
-    st = _L.gg_genome_stats_files(arr, n, int(threads), _ptr(out))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_genome_stats_files, arr, n, int(threads), _ptr(out))
     return _stats_list(out[:n])
 
 
@@ -908,11 +917,9 @@ class Packed:
 
 
 def pack_files(paths, k=21, threads=0):
-    arr = (ctypes.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+    arr = (_str * len(paths))(*[os.fsencode(p) for p in paths])  # (no entry for no path: not _paths_arg's array)
     out = ctypes.POINTER(_Packed)()
-    st = _L.gg_pack_files(arr, len(paths), k, threads, ctypes.byref(out))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_pack_files, arr, len(paths), k, threads, _byref(out))
     return Packed(out)
 
 
@@ -928,27 +935,18 @@ def pack_records(genomes, k=21):
     lens = np.array([len(r) for r in recs] or [0], dtype=np.uint64)
     gids = np.array(gid or [0], dtype=np.uint32)
     out = ctypes.POINTER(_Packed)()
-    st = _L.gg_pack_records(seqs, _ptr(lens), _ptr(gids), len(recs), len(genomes), k, ctypes.byref(out))
-    if st != GG_OK:
-        raise _thread_err(st)
+    _tcall(_L.gg_pack_records, seqs, _ptr(lens), _ptr(gids), len(recs), len(genomes), k, _byref(out))
     return Packed(out)
-
-
-def _take_pairs(ptr, n):
-    if n == 0:
-        _L.gg_free(ptr)
-        return np.zeros(0, dtype=PAIR_DTYPE)
-    # one memmove into a fresh array (a ctypes array type per call, or
-    # np.ctypeslib.as_array, cost ~0.1-0.25 ms at C3's 15k pairs)
-    out = np.empty(n, dtype=PAIR_DTYPE)
-    ctypes.memmove(out.ctypes.data, ptr.value, n * PAIR_DTYPE.itemsize)
-    _L.gg_free(ptr)
-    return out
 
 
 def _dev_ptr(t):
     """Device pointer of a torch tensor or an int."""
     return t if isinstance(t, int) else t.data_ptr()
+
+
+def _dev_opt(t):
+    """_dev_ptr of an optional buffer: None is NULL."""
+    return None if t is None else _dev_ptr(t)
 
 
 def device_runs(runs, device):
@@ -989,12 +987,12 @@ class Context:
     def __init__(self, k=21, sketch_size=1000, seed=0, device=-1, devices=None, host_threads=0):
         st = _i32()
         if devices is None:
-            self._c = _L.gg_create(k, sketch_size, seed, device, ctypes.byref(st))
+            self._c = _L.gg_create(k, sketch_size, seed, device, _byref(st))
         elif devices == "all":
-            self._c = _L.gg_create_multi(k, sketch_size, seed, None, 0, ctypes.byref(st))
+            self._c = _L.gg_create_multi(k, sketch_size, seed, None, 0, _byref(st))
         else:
             arr = (ctypes.c_int * max(len(devices), 1))(*devices)
-            self._c = _L.gg_create_multi(k, sketch_size, seed, arr, len(devices), ctypes.byref(st))
+            self._c = _L.gg_create_multi(k, sketch_size, seed, arr, len(devices), _byref(st))
         if not self._c:
             raise _thread_err(st.value)
         self.k, self.s, self.seed = k, sketch_size, seed
@@ -1021,6 +1019,19 @@ class Context:
     def _err(self, st):
         return GalahGpuError(st, _L.gg_last_error(self._c).decode(errors="replace"))
 
+    def _hcall(self, fn, handle, *args):
+        """fn(handle, *args) of an entry point that reports on this context:
+        the gg_collection_* calls on a collection's handle."""
+        st = fn(handle, *args)
+        if st != GG_OK:
+            raise self._err(st)
+
+    def _call(self, fn, *args):
+        """fn(this context, *args)."""
+        self._hcall(fn, self._c, *args)
+
+    _pairs_ani = staticmethod(_take_pairs_ani)
+
     @property
     def device(self):
         return _L.gg_device(self._c)
@@ -1043,17 +1054,17 @@ class Context:
 
     def set_host_threads(self, n):
         """galah --threads (CAP:1327-1332): host threads for file ingest (<= 0: default)."""
-        st = _L.gg_set_host_threads(self._c, int(n))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_set_host_threads, int(n))
+
+    def _counters(self, fn, count, dtype=np.uint64):
+        """A read-out's array of `count` counters."""
+        out = np.zeros(count, dtype)
+        self._call(fn, _ptr(out))
+        return out
 
     def phase_times(self):
         """Wall-clock ms of the last fused call's phases (PHASES)."""
-        out = np.zeros(len(PHASES), np.float64)
-        st = _L.gg_phase_times(self._c, _ptr(out))
-        if st != GG_OK:
-            raise self._err(st)
-        return dict(zip(PHASES, out.tolist()))
+        return dict(zip(PHASES, self._counters(_L.gg_phase_times, len(PHASES), np.float64).tolist()))
 
     def precluster_shards(self, shards, min_ani):
         """shards: one (d_words tensor, runs, n_genomes) per member,
@@ -1073,97 +1084,56 @@ class Context:
             arr[x].runs = rp
             arr[x].n_runs = nr
             arr[x].n_genomes = int(ng)
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_precluster_shards(self._c, arr, ctypes.c_float(min_ani), ctypes.byref(pp), ctypes.byref(ap),
-                                     ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return self._pairs_ani(pp, ap, cnt.value)
-
-    @staticmethod
-    def _pairs_ani(pp, ap, n):
-        if n:
-            ani = np.empty(n, np.float32)
-            ctypes.memmove(ani.ctypes.data, ap.value, n * 4)
-        else:
-            ani = np.zeros(0, np.float32)
-        _L.gg_free(ap)
-        return _take_pairs(pp, n), ani
+        out = _PairsOut()
+        self._call(_L.gg_precluster_shards, arr, _f32(min_ani), *out.refs)
+        return out.take()
 
     def timing_enable(self, on=True):
-        st = _L.gg_timing_enable(self._c, 1 if on else 0)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_timing_enable, 1 if on else 0)
 
     def pair_paths(self):
         """Which pair kernel ran, counted since the context was created
         (gg_pair_paths): {"index", "index_abandoned", "gate", "other",
         "index_full_sort"} ("index_full_sort" counts the index calls that
         used the full sort instead of the bucketed build)."""
-        out = np.zeros(5, np.uint64)
-        st = _L.gg_pair_paths(self._c, _ptr(out))
-        if st != GG_OK:
-            raise self._err(st)
+        out = self._counters(_L.gg_pair_paths, 5)
         return dict(zip(("index", "index_abandoned", "gate", "other", "index_full_sort"), (int(x) for x in out)))
 
     def fallbacks(self):
         """Slow paths taken since the context was created (gg_fallbacks):
         {"index_to_gate", "index_full_sort", "peer_staged", "sketch_retry", "inflate_host", "sketch_set"}."""
-        out = np.zeros(len(FALLBACKS), np.uint64)
-        st = _L.gg_fallbacks(self._c, _ptr(out))
-        if st != GG_OK:
-            raise self._err(st)
-        return dict(zip(FALLBACKS, (int(x) for x in out)))
+        return dict(zip(FALLBACKS, (int(x) for x in self._counters(_L.gg_fallbacks, len(FALLBACKS)))))
 
     def peer_links(self):
         """[M, M] int array (gg_peer_links): 1 = member a copies from member b
         device to device, 0 = staged through host memory."""
         M = self.device_count
-        out = np.zeros(M * M, np.int32)
-        st = _L.gg_peer_links(self._c, _ptr(out))
-        if st != GG_OK:
-            raise self._err(st)
-        return out.reshape(M, M)
+        return self._counters(_L.gg_peer_links, M * M, np.int32).reshape(M, M)
 
     def info_line(self):
         """The one-line summary galah would log at info! after distances()."""
         buf = ctypes.create_string_buffer(1024)
-        st = _L.gg_info_line(self._c, buf, len(buf))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_info_line, buf, len(buf))
         return buf.value.decode()
 
     def timing_read(self, kernel):
         """-> dict(ms, launches, work) summed since timing_enable."""
         k = _KStats()
-        st = _L.gg_timing_read(self._c, kernel, ctypes.byref(k))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_timing_read, kernel, _byref(k))
         return {"ms": k.ms, "launches": k.launches, "work": k.work}
 
     # -- host-buffer API -------------------------------------------------
     def sketch(self, packed):
         """-> (sketches [n_genomes, s] u64 padded with 0, lens [n] u32)."""
-        ng = packed.n_genomes
-        out = np.zeros((max(ng, 1), self.s), dtype=np.uint64)
-        lens = np.zeros(max(ng, 1), dtype=np.uint32)
-        st = _L.gg_sketch(self._c, packed._p, _ptr(out), _ptr(lens))
-        if st != GG_OK:
-            raise self._err(st)
-        return out[:ng], lens[:ng]
+        op, lp, out, lens = _rows_out(packed.n_genomes, self.s)
+        self._call(_L.gg_sketch, packed._p, op, lp)
+        return out, lens
 
     def pairs(self, sketches, lens, min_ani):
-        sk = np.ascontiguousarray(sketches, dtype=np.uint64)
-        ln = np.ascontiguousarray(lens, dtype=np.uint32)
-        n = ln.shape[0]
-        if n and sk.shape != (n, self.s):
-            raise ValueError("sketches must be [n, sketch_size]")
-        outp, cnt = _vp(), _u64()
-        st = _L.gg_pairs(self._c, _ptr(sk), _ptr(ln), n, ctypes.c_float(min_ani), ctypes.byref(outp),
-                         ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return _take_pairs(outp, cnt.value)
+        sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
+        out = _PairsOut(ani=False)
+        self._call(_L.gg_pairs, _ptr(sk), _ptr(ln), n, _f32(min_ani), *out.refs)
+        return out.take()
 
     def pairs_border(self, sketches, lens, n_old, min_ani):
         """The border of a sketch matrix (gg_pairs_border): the passing pairs
@@ -1171,12 +1141,9 @@ class Context:
         to pairs(sketches[:n_old]).  On the context's (first) device; only the
         new rows are evaluated."""
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
-        outp, cnt = _vp(), _u64()
-        st = _L.gg_pairs_border(self._c, _ptr(sk), _ptr(ln), n, int(n_old), ctypes.c_float(min_ani),
-                                ctypes.byref(outp), ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return _take_pairs(outp, cnt.value)
+        out = _PairsOut(ani=False)
+        self._call(_L.gg_pairs_border, _ptr(sk), _ptr(ln), n, int(n_old), _f32(min_ani), *out.refs)
+        return out.take()
 
     def update_files(self, old_sketches, old_lens, new_paths, min_ani, cache_dir=None):
         """A finished run carried forward (gg_update_files): only new_paths are
@@ -1185,27 +1152,19 @@ class Context:
         border pairs sorted by (i, j) with indices into old + new, their f32
         ANI)."""
         sk, ln, n_old, _ = _rows_arg(old_sketches, old_lens, self.s)
-        n_new = len(new_paths)
-        arr = (ctypes.c_char_p * max(n_new, 1))(*[os.fsencode(p) for p in new_paths])
-        out = np.zeros((max(n_new, 1), self.s), dtype=np.uint64)
-        lens = np.zeros(max(n_new, 1), dtype=np.uint32)
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_update_files(self._c, _ptr(sk), _ptr(ln), n_old, arr, n_new, ctypes.c_float(min_ani),
-                                None if cache_dir is None else os.fsencode(cache_dir), _ptr(out), _ptr(lens),
-                                ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
-        return out[:n_new], lens[:n_new], pairs, ani
+        arr, n_new = _paths_arg(new_paths)
+        op, lp, out, lens = _rows_out(n_new, self.s)
+        border = _PairsOut()
+        self._call(_L.gg_update_files, _ptr(sk), _ptr(ln), n_old, arr, n_new, _f32(min_ani), _dir_arg(cache_dir), op, lp,
+                   *border.refs)
+        pairs, ani = border.take()
+        return out, lens, pairs, ani
 
     # ---- a collection resident on the device (gg_collection_*; class Collection wraps a handle)
     def collection_create(self, min_ani, reserve_rows=0, reserve_pairs=0):
         """An empty resident collection at min_ani -> its handle (collection_destroy frees it)."""
         h = _vp()
-        st = _L.gg_collection_create(self._c, ctypes.c_float(min_ani), int(reserve_rows), int(reserve_pairs),
-                                     ctypes.byref(h))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_collection_create, _f32(min_ani), int(reserve_rows), int(reserve_pairs), _byref(h))
         return h.value
 
     def collection_load(self, sketches, lens, pairs, ani, min_ani):
@@ -1217,10 +1176,7 @@ class Context:
         if len(pa) != len(an):
             raise ValueError("one ANI value per pair")
         h = _vp()
-        st = _L.gg_collection_load(self._c, _ptr(sk), _ptr(ln), n, _ptr(pa), _ptr(an), len(pa),
-                                   ctypes.c_float(min_ani), ctypes.byref(h))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_collection_load, _ptr(sk), _ptr(ln), n, _ptr(pa), _ptr(an), len(pa), _f32(min_ani), _byref(h))
         return h.value
 
     def collection_destroy(self, handle):
@@ -1228,91 +1184,72 @@ class Context:
 
     def collection_stat(self, handle):
         """-> ({n_pairs, pair_capacity, device_bytes, n_rows, row_capacity, grows, rows_moved}, min_ani f32)."""
-        info, thr = _CollectionInfo(), ctypes.c_float()
-        st = _L.gg_collection_stat(handle, ctypes.byref(info), ctypes.byref(thr))
-        if st != GG_OK:
-            raise _thread_err(st)
+        info, thr = _CollectionInfo(), _f32()
+        _tcall(_L.gg_collection_stat, handle, _byref(info), _byref(thr))  # (reports on the thread)
         return info.as_dict(), np.float32(thr.value)
+
+    def _n_rows(self, handle):
+        return self.collection_stat(handle)[0]["n_rows"]
 
     def collection_add_rows(self, handle, sketches, lens):
         """Host rows appended -> the number of border pairs added."""
         sk, ln, n_new, _ = _rows_arg(sketches, lens, self.s)
         added = _u64()
-        st = _L.gg_collection_add_rows(handle, _ptr(sk), _ptr(ln), n_new, ctypes.byref(added))
-        if st != GG_OK:
-            raise self._err(st)
+        self._hcall(_L.gg_collection_add_rows, handle, _ptr(sk), _ptr(ln), n_new, _byref(added))
         return added.value
 
     def collection_add_rows_device(self, handle, d_sketches, d_lens, n_new, stream=None):
         """Device rows (tensors or pointers) appended -> the number of border pairs added."""
         added = _u64()
-        st = _L.gg_collection_add_rows_device(handle, _dev_ptr(d_sketches), _dev_ptr(d_lens), int(n_new),
-                                              ctypes.byref(added), stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._hcall(_L.gg_collection_add_rows_device, handle, _dev_ptr(d_sketches), _dev_ptr(d_lens), int(n_new),
+                    _byref(added), stream)
         return added.value
 
     def collection_add_files(self, handle, paths, cache_dir=None):
         """Files sketched (cache_dir as sketch_files) and appended -> the number of border pairs added."""
-        n_new = len(paths)
-        arr = (ctypes.c_char_p * max(n_new, 1))(*[os.fsencode(p) for p in paths])
+        arr, n_new = _paths_arg(paths)
         added = _u64()
-        st = _L.gg_collection_add_files(handle, arr, n_new, None if cache_dir is None else os.fsencode(cache_dir),
-                                        ctypes.byref(added))
-        if st != GG_OK:
-            raise self._err(st)
+        self._hcall(_L.gg_collection_add_files, handle, arr, n_new, _dir_arg(cache_dir), _byref(added))
         return added.value
 
     def collection_remove(self, handle, rows):
         """Rows (any order, repeats allowed) removed -> new_index [n before]
         u32, 0xFFFFFFFF for a removed row."""
         rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
-        n = self.collection_stat(handle)[0]["n_rows"]
+        n = self._n_rows(handle)
         new_index = np.zeros(max(n, 1), np.uint32)
-        st = _L.gg_collection_remove(handle, _ptr(rows) if len(rows) else None, len(rows), _ptr(new_index))
-        if st != GG_OK:
-            raise self._err(st)
+        self._hcall(_L.gg_collection_remove, handle, _ptr(rows) if len(rows) else None, len(rows), _ptr(new_index))
         return new_index[:n]
 
     def collection_cluster(self, handle, cluster_ani, order=None):
         """rep_of [n] u32 (positions in order; order: position -> row, None: identity)."""
-        n = self.collection_stat(handle)[0]["n_rows"]
+        n = self._n_rows(handle)
         if order is not None:
             order = np.ascontiguousarray(order, dtype=np.uint32).reshape(-1)
             if len(order) != n:
                 raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
         rep_of = np.zeros(max(n, 1), np.uint32)
-        st = _L.gg_collection_cluster(handle, None if order is None or n == 0 else _ptr(order),
-                                      ctypes.c_float(cluster_ani), _ptr(rep_of))
-        if st != GG_OK:
-            raise self._err(st)
+        self._hcall(_L.gg_collection_cluster, handle, None if order is None or n == 0 else _ptr(order),
+                    _f32(cluster_ani), _ptr(rep_of))
         return rep_of[:n]
 
     def collection_pairs(self, handle):
         """-> (pairs sorted by (i, j), ani f32)."""
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_collection_pairs(handle, ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return self._pairs_ani(pp, ap, cnt.value)
+        out = _PairsOut()
+        self._hcall(_L.gg_collection_pairs, handle, *out.refs)
+        return out.take()
 
     def collection_rows(self, handle):
         """-> (sketches [n, s] u64, lens [n] u32)."""
-        n = self.collection_stat(handle)[0]["n_rows"]
-        out = np.zeros((max(n, 1), self.s), dtype=np.uint64)
-        lens = np.zeros(max(n, 1), dtype=np.uint32)
-        st = _L.gg_collection_rows(handle, _ptr(out), _ptr(lens))
-        if st != GG_OK:
-            raise self._err(st)
-        return out[:n], lens[:n]
+        op, lp, out, lens = _rows_out(self._n_rows(handle), self.s)
+        self._hcall(_L.gg_collection_rows, handle, op, lp)
+        return out, lens
 
     def collection_view(self, handle):
         """Device pointers (ints) of the sketches, lens, pairs and ANI, valid
         until the next call that changes the collection."""
         p = [_vp(), _vp(), _vp(), _vp()]
-        st = _L.gg_collection_view(handle, *[ctypes.byref(x) for x in p])
-        if st != GG_OK:
-            raise _thread_err(st)
+        _tcall(_L.gg_collection_view, handle, *[_byref(x) for x in p])  # (reports on the thread)
         return tuple(x.value or 0 for x in p)
 
     # ---- the query: hits and nearest representative of genomes that are not added (gg_query_*)
@@ -1321,130 +1258,86 @@ class Context:
         the cells (row i, query q) that pass at min_ani."""
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
         qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, self.s)
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_query_rows(self._c, _ptr(sk), _ptr(ln), n, _ptr(qs), _ptr(ql), nq, ctypes.c_float(min_ani),
-                              ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return self._pairs_ani(pp, ap, cnt.value)
+        out = _PairsOut()
+        self._call(_L.gg_query_rows, _ptr(sk), _ptr(ln), n, _ptr(qs), _ptr(ql), nq, _f32(min_ani), *out.refs)
+        return out.take()
 
     def query_rows_device(self, d_sketches, d_lens, n, d_q_sketches, d_q_lens, nq, min_ani, d_out, out_cap, d_count,
                           stream=None):
         """Device rows and queries (tensors or pointers): the passing cells
         appended to d_out by pairs_device's output contract."""
-        st = _L.gg_query_rows_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), int(n), _dev_ptr(d_q_sketches),
-                                     _dev_ptr(d_q_lens), int(nq), ctypes.c_float(min_ani),
-                                     None if d_out is None else _dev_ptr(d_out), int(out_cap), _dev_ptr(d_count),
-                                     stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_query_rows_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), int(n), _dev_ptr(d_q_sketches),
+                   _dev_ptr(d_q_lens), int(nq), _f32(min_ani), _dev_opt(d_out), int(out_cap), _dev_ptr(d_count), stream)
 
     def query_best_device(self, n, nq, d_pairs, d_ani, n_pairs, d_rank, d_best, d_best_ani, stream=None):
         """Every query's best candidate from device hits (any order); d_rank may be None."""
-        st = _L.gg_query_best_device(self._c, int(n), int(nq), _dev_ptr(d_pairs), _dev_ptr(d_ani), int(n_pairs),
-                                     None if d_rank is None else _dev_ptr(d_rank), _dev_ptr(d_best),
-                                     _dev_ptr(d_best_ani), stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_query_best_device, int(n), int(nq), _dev_ptr(d_pairs), _dev_ptr(d_ani), int(n_pairs),
+                   _dev_opt(d_rank), _dev_ptr(d_best), _dev_ptr(d_best_ani), stream)
 
     def collection_query_rows(self, handle, q_sketches, q_lens, min_ani):
         """Host queries against a collection (unchanged by it) -> (pairs, ani)."""
         qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, self.s)
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_collection_query_rows(handle, _ptr(qs), _ptr(ql), nq, ctypes.c_float(min_ani), ctypes.byref(pp),
-                                         ctypes.byref(ap), ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return self._pairs_ani(pp, ap, cnt.value)
+        out = _PairsOut()
+        self._hcall(_L.gg_collection_query_rows, handle, _ptr(qs), _ptr(ql), nq, _f32(min_ani), *out.refs)
+        return out.take()
 
     def collection_query_files(self, handle, paths, min_ani, cache_dir=None, want_sketches=False):
         """Files sketched (cache_dir as sketch_files) and queried -> (pairs,
         ani), or (pairs, ani, sketches [nq, s], lens [nq]) with want_sketches."""
-        nq = len(paths)
-        arr = (ctypes.c_char_p * max(nq, 1))(*[os.fsencode(p) for p in paths])
-        out = np.zeros((max(nq, 1), self.s), dtype=np.uint64) if want_sketches else None
-        lens = np.zeros(max(nq, 1), dtype=np.uint32) if want_sketches else None
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_collection_query_files(handle, arr, nq, None if cache_dir is None else os.fsencode(cache_dir),
-                                          ctypes.c_float(min_ani), None if out is None else _ptr(out),
-                                          None if lens is None else _ptr(lens), ctypes.byref(pp), ctypes.byref(ap),
-                                          ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
-        return (pairs, ani, out[:nq], lens[:nq]) if want_sketches else (pairs, ani)
+        arr, nq = _paths_arg(paths)
+        op, lp, sk, lens = _rows_out(nq, self.s) if want_sketches else (None, None, None, None)
+        out = _PairsOut()
+        self._hcall(_L.gg_collection_query_files, handle, arr, nq, _dir_arg(cache_dir), _f32(min_ani), op, lp, *out.refs)
+        pairs, ani = out.take()
+        return (pairs, ani, sk, lens) if want_sketches else (pairs, ani)
 
     def collection_classify_rows(self, handle, q_sketches, q_lens, rank=None):
         """Every host query's best candidate at the collection's min_ani -> (best [nq], best_ani [nq])."""
         qs, ql, nq, _ = _rows_arg(q_sketches, q_lens, self.s)
-        n = self.collection_stat(handle)[0]["n_rows"]
-        rank = _rank_arg(rank, n)
-        best = np.zeros(max(nq, 1), dtype=PAIR_DTYPE)
-        best_ani = np.zeros(max(nq, 1), dtype=np.float32)
-        st = _L.gg_collection_classify_rows(handle, _ptr(qs), _ptr(ql), nq, None if rank is None or n == 0 else _ptr(rank),
-                                            _ptr(best), _ptr(best_ani))
-        if st != GG_OK:
-            raise self._err(st)
-        return best[:nq], best_ani[:nq]
+        rank, rp = _rank_arg(rank, self._n_rows(handle))
+        bp, bap, best, best_ani = _best_out(nq)
+        self._hcall(_L.gg_collection_classify_rows, handle, _ptr(qs), _ptr(ql), nq, rp, bp, bap)
+        return best, best_ani
 
     def collection_classify_files(self, handle, paths, rank=None, cache_dir=None):
         """Every file's best candidate at the collection's min_ani -> (best [nq], best_ani [nq])."""
-        nq = len(paths)
-        arr = (ctypes.c_char_p * max(nq, 1))(*[os.fsencode(p) for p in paths])
-        n = self.collection_stat(handle)[0]["n_rows"]
-        rank = _rank_arg(rank, n)
-        best = np.zeros(max(nq, 1), dtype=PAIR_DTYPE)
-        best_ani = np.zeros(max(nq, 1), dtype=np.float32)
-        st = _L.gg_collection_classify_files(handle, arr, nq, None if cache_dir is None else os.fsencode(cache_dir),
-                                             None if rank is None or n == 0 else _ptr(rank), _ptr(best), _ptr(best_ani))
-        if st != GG_OK:
-            raise self._err(st)
-        return best[:nq], best_ani[:nq]
+        arr, nq = _paths_arg(paths)
+        rank, rp = _rank_arg(rank, self._n_rows(handle))
+        bp, bap, best, best_ani = _best_out(nq)
+        self._hcall(_L.gg_collection_classify_files, handle, arr, nq, _dir_arg(cache_dir), rp, bp, bap)
+        return best, best_ani
 
     def sketch_files(self, paths, cache_dir=None):
         """finch sketch_files (src/finch.rs:47) for files -> (sketches [n, s] u64
         padded with 0, lens [n] u32, number of genomes served by cache_dir)."""
-        n = len(paths)
-        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
-        out = np.zeros((max(n, 1), self.s), dtype=np.uint64)
-        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        arr, n = _paths_arg(paths)
+        op, lp, out, lens = _rows_out(n, self.s)
         hits = _u32()
-        st = _L.gg_sketch_files(self._c, arr, n, None if cache_dir is None else os.fsencode(cache_dir),
-                                _ptr(out), _ptr(lens), ctypes.byref(hits))
-        if st != GG_OK:
-            raise self._err(st)
-        return out[:n], lens[:n], hits.value
+        self._call(_L.gg_sketch_files, arr, n, _dir_arg(cache_dir), op, lp, _byref(hits))
+        return out, lens, hits.value
 
     def sketch_files_stats(self, paths, cache_dir=None):
         """sketch_files plus every genome's GenomeAssemblyStats from the same
         read of each file (gg_sketch_files_stats) -> (sketches, lens, stats).
         cache_dir is written, never read: a later precluster_files over the
         same files, in any order, finds every sketch there."""
-        n = len(paths)
-        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
-        out = np.zeros((max(n, 1), self.s), dtype=np.uint64)
-        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        arr, n = _paths_arg(paths)
+        op, lp, out, lens = _rows_out(n, self.s)
         stats = np.zeros(max(n, 1), dtype=STATS_DTYPE)
-        st = _L.gg_sketch_files_stats(self._c, arr, n, None if cache_dir is None else os.fsencode(cache_dir),
-                                      _ptr(out), _ptr(lens), _ptr(stats))
-        if st != GG_OK:
-            raise self._err(st)
-        return out[:n], lens[:n], _stats_list(stats[:n])
+        self._call(_L.gg_sketch_files_stats, arr, n, _dir_arg(cache_dir), op, lp, _ptr(stats))
+        return out, lens, _stats_list(stats[:n])
 
     def precluster_files(self, paths, min_ani, cache_dir=None):
         """-> (pairs structured array sorted by (i, j), ani f32 array).  With
         cache_dir, genomes sketched by an earlier call are read from the
         sketch cache (self.last_cached counts them)."""
-        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
-        pp, ap, cnt, hits = _vp(), _vp(), _u64(), _u32()
-        st = _L.gg_precluster_files_cached(self._c, arr, len(paths), ctypes.c_float(min_ani),
-                                           None if cache_dir is None else os.fsencode(cache_dir),
-                                           ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt),
-                                           ctypes.byref(hits))
-        self.last_cached = hits.value
+        arr, n = _paths_arg(paths)
+        out, hits = _PairsOut(), _u32()
+        st = _L.gg_precluster_files_cached(self._c, arr, n, _f32(min_ani), _dir_arg(cache_dir), *out.refs, _byref(hits))
+        self.last_cached = hits.value  # (written on failure too, before the status is looked at)
         if st != GG_OK:
             raise self._err(st)
-        return self._pairs_ani(pp, ap, cnt.value)
+        return out.take()
 
     def precluster_files_resident(self, paths, min_ani, cache_dir=None):
         """precluster_files with the rows resident on the (first) device
@@ -1452,16 +1345,11 @@ class Context:
         (set_pairs_path), sorted and given their f32 ANI on the device ->
         (pairs, ani, summary dict of gg_pairs_matrix_summary).  pairs and ani
         equal precluster_files' whatever the path."""
-        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        summary = _PairsMatrixSummary()
-        st = _L.gg_precluster_files_resident(self._c, arr, len(paths), ctypes.c_float(min_ani),
-                                             None if cache_dir is None else os.fsencode(cache_dir),
-                                             ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt),
-                                             ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
-        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
+        arr, n = _paths_arg(paths)
+        out, summary = _PairsOut(), _PairsMatrixSummary()
+        self._call(_L.gg_precluster_files_resident, arr, n, _f32(min_ani), _dir_arg(cache_dir), *out.refs,
+                   _byref(summary))
+        pairs, ani = out.take()
         return pairs, ani, summary.as_dict()
 
     def pairs_matrix(self, sketches, lens, min_ani, rows=None):
@@ -1473,16 +1361,12 @@ class Context:
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
         if rows is None:
             r, rp, m = None, None, n
-        else:
+        else:  # (not _matrix_rows_arg: rows is not flattened here, a 2-D rows counts its first axis)
             r = np.ascontiguousarray(rows, dtype=np.uint32)
             rp, m = _ptr(r), len(r)
-        outp, cnt = _vp(), _u64()
-        summary = _PairsMatrixSummary()
-        st = _L.gg_pairs_matrix(self._c, _ptr(sk), _ptr(ln), n, rp, m, ctypes.c_float(min_ani), ctypes.byref(outp),
-                                ctypes.byref(cnt), ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
-        return _take_pairs(outp, cnt.value), summary.as_dict()
+        out, summary = _PairsOut(ani=False), _PairsMatrixSummary()
+        self._call(_L.gg_pairs_matrix, _ptr(sk), _ptr(ln), n, rp, m, _f32(min_ani), *out.refs, _byref(summary))
+        return out.take(), summary.as_dict()
 
     def pairs_border_matrix(self, sketches, lens, n_old, min_ani):
         """pairs_border() by the border form of the matrix product
@@ -1490,13 +1374,10 @@ class Context:
         dense set -> (pairs sorted by (i, j), summary dict of
         gg_pairs_matrix_summary; its column counts are the border's)."""
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
-        outp, cnt = _vp(), _u64()
-        summary = _PairsMatrixSummary()
-        st = _L.gg_pairs_border_matrix(self._c, _ptr(sk), _ptr(ln), n, int(n_old), ctypes.c_float(min_ani),
-                                       ctypes.byref(outp), ctypes.byref(cnt), ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
-        return _take_pairs(outp, cnt.value), summary.as_dict()
+        out, summary = _PairsOut(ani=False), _PairsMatrixSummary()
+        self._call(_L.gg_pairs_border_matrix, _ptr(sk), _ptr(ln), n, int(n_old), _f32(min_ani), *out.refs,
+                   _byref(summary))
+        return out.take(), summary.as_dict()
 
     def set_pairs_path(self, path):
         """What produces the pairs inside cluster_rows_device,
@@ -1509,9 +1390,7 @@ class Context:
         if path not in PAIRS_PATHS:
             raise ValueError("pairs path must be one of %s, not %r" % (", ".join(PAIRS_PATHS), path))
         before = self.pairs_path
-        st = _L.gg_set_pairs_path(self._c, PAIRS_PATHS.index(path))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_set_pairs_path, PAIRS_PATHS.index(path))
         return before
 
     @property
@@ -1521,20 +1400,13 @@ class Context:
     def pairs_paths_taken(self):
         """Calls that needed pairs of resident rows since creation, by what
         ran: {"default", "matrix", "auto"} (auto: the matrix by AUTO's choice)."""
-        c = np.zeros(3, np.uint64)
-        st = _L.gg_pairs_paths_taken(self._c, _ptr(c))
-        if st != GG_OK:
-            raise self._err(st)
-        return {k: int(v) for k, v in zip(PAIRS_PATHS, c)}
+        return {k: int(v) for k, v in zip(PAIRS_PATHS, self._counters(_L.gg_pairs_paths_taken, 3))}
 
     def cluster_pairs(self, n_genomes, pairs, ani, cluster_ani):
         """cluster_pairs_host on the context's (first) device -> rep_of."""
         p, a = _pairs_ani_arg(pairs, ani)
         rep_of = np.zeros(max(n_genomes, 1), np.uint32)
-        st = _L.gg_cluster_pairs(self._c, n_genomes, _ptr(p), _ptr(a), len(p), ctypes.c_float(cluster_ani),
-                                 _ptr(rep_of))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_cluster_pairs, n_genomes, _ptr(p), _ptr(a), len(p), _f32(cluster_ani), _ptr(rep_of))
         return rep_of[:n_genomes]
 
     def preclusters(self, n_genomes, pairs, with_pairs=True):
@@ -1548,10 +1420,8 @@ class Context:
         local = np.zeros(max(len(p), 1), LOCAL_PAIR_DTYPE) if with_pairs else None
         poff = np.zeros(n_genomes + 1, np.uint64) if with_pairs else None
         ns = _u32()
-        st = _L.gg_preclusters(self._c, n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), ctypes.byref(ns),
-                               _ptr(local) if with_pairs else None, _ptr(poff) if with_pairs else None)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_preclusters, n_genomes, _ptr(p), len(p), _ptr(members), _ptr(offsets), _byref(ns),
+                   _ptr(local) if with_pairs else None, _ptr(poff) if with_pairs else None)
         members, offsets = members[:n_genomes], offsets[:ns.value + 1].copy()
         if not with_pairs:
             return members, offsets, None, None
@@ -1563,9 +1433,7 @@ class Context:
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
         p = _pair_list_arg(pairs)
         ani = np.zeros(max(len(p), 1), np.float32)
-        st = _L.gg_ani_pairs(self._c, _ptr(sk), _ptr(ln), n, _ptr(p), len(p), _ptr(ani))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_pairs, _ptr(sk), _ptr(ln), n, _ptr(p), len(p), _ptr(ani))
         return p, ani[:len(p)]
 
     def ani_matrix(self, sketches, lens, rows=None):
@@ -1576,23 +1444,19 @@ class Context:
         r, rp, m = _matrix_rows_arg(rows, n)
         common, total, ani = _matrix_out(m)
         summary = _MatrixSummary()
-        st = _L.gg_ani_matrix(self._c, _ptr(sk), _ptr(ln), n, rp, m, _ptr(common), _ptr(total), _ptr(ani),
-                              ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_matrix, _ptr(sk), _ptr(ln), n, rp, m, _ptr(common), _ptr(total), _ptr(ani),
+                   _byref(summary))
         return common[:m, :m], total[:m, :m], ani[:m, :m], summary.as_dict()
 
     def ani_matrix_files(self, paths, cache_dir=None):
         """sketch_files(paths, cache_dir) followed by ani_matrix over all rows
         (gg_ani_matrix_files) -> (common, total, ani, summary dict)."""
-        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
-        m = len(paths)
+        arr, m = _paths_arg(paths)
         common, total, ani = _matrix_out(m)
         summary = _MatrixSummary()
-        st = _L.gg_ani_matrix_files(self._c, arr, m, os.fsencode(cache_dir) if cache_dir else None, _ptr(common),
-                                    _ptr(total), _ptr(ani), ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
+        # (not _dir_arg: "" is NULL in this call and in precluster_matrices_files)
+        self._call(_L.gg_ani_matrix_files, arr, m, os.fsencode(cache_dir) if cache_dir else None, _ptr(common),
+                   _ptr(total), _ptr(ani), _byref(summary))
         return common[:m, :m], total[:m, :m], ani[:m, :m], summary.as_dict()
 
     def ani_matrix_groups(self, sketches, lens, members, offsets=None):
@@ -1606,15 +1470,10 @@ class Context:
         ani_f32_device -- reaches the same cells faster (0.36 against
         1.64 ms on 10,000 rows in groups of 10); above it this call wins."""
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
-        mem, off, ng = _groups_arg(members, offsets)
-        cells = ani_matrix_group_cells(off)
-        z = max(int(cells[-1]), 1)
-        common, total, ani = np.zeros(z, np.uint32), np.zeros(z, np.uint32), np.zeros(z, np.float32)
+        mem, off, ng, cells, common, total, ani = _groups_out(members, offsets)
         summary = _MatrixSummary()
-        st = _L.gg_ani_matrix_groups(self._c, _ptr(sk), _ptr(ln), n, _ptr(mem), _ptr(off), ng, _ptr(common),
-                                     _ptr(total), _ptr(ani), ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_matrix_groups, _ptr(sk), _ptr(ln), n, _ptr(mem), _ptr(off), ng, _ptr(common), _ptr(total),
+                   _ptr(ani), _byref(summary))
         z = int(cells[-1])
         return common[:z], total[:z], ani[:z], cells, summary.as_dict()
 
@@ -1624,33 +1483,21 @@ class Context:
         at min_ani, the partition and the grouped matrices on the resident
         rows -> (members, offsets, cell_offsets, common, total, ani, summary
         dict); the groups are preclusters()' (largest first)."""
-        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        arr, n = _paths_arg(paths)
         mem, off, cel, com, tot, an = _vp(), _vp(), _vp(), _vp(), _vp(), _vp()
         ng = _u32()
         summary = _MatrixSummary()
-        st = _L.gg_precluster_matrices_files(self._c, arr, len(paths), ctypes.c_float(min_ani),
-                                             os.fsencode(cache_dir) if cache_dir else None, ctypes.byref(mem),
-                                             ctypes.byref(off), ctypes.byref(ng), ctypes.byref(cel), ctypes.byref(com),
-                                             ctypes.byref(tot), ctypes.byref(an), ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
-
-        def take(p, count, dtype):
-            try:
-                if not count:
-                    return np.zeros(0, dtype)
-                return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)),
-                                             shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
-            finally:
-                _L.gg_free(p)
-
-        offsets = take(off, ng.value + 1, np.uint32)
-        cells = take(cel, ng.value + 1, np.uint64)
+        # (not _dir_arg: "" is NULL in this call and in ani_matrix_files)
+        self._call(_L.gg_precluster_matrices_files, arr, n, _f32(min_ani), os.fsencode(cache_dir) if cache_dir else None,
+                   _byref(mem), _byref(off), _byref(ng), _byref(cel), _byref(com), _byref(tot), _byref(an),
+                   _byref(summary))
+        offsets = _take_array(off, ng.value + 1, np.uint32)
+        cells = _take_array(cel, ng.value + 1, np.uint64)
         # (members is allocated for one entry at least; every buffer is released)
-        members = take(mem, len(paths), np.uint32)
+        members = _take_array(mem, n, np.uint32)
         z = int(cells[-1])
-        return (members, offsets, cells, take(com, z, np.uint32), take(tot, z, np.uint32), take(an, z, np.float32),
-                summary.as_dict())
+        return (members, offsets, cells, _take_array(com, z, np.uint32), _take_array(tot, z, np.uint32),
+                _take_array(an, z, np.float32), summary.as_dict())
 
     def validate_clusters(self, sketches, lens, clusters, ani):
         """validate_clusters_host on the device (gg_validate_clusters): the
@@ -1658,45 +1505,33 @@ class Context:
         the all-pairs path -> Validation."""
         sk, ln, n, _ = _rows_arg(sketches, lens, self.s)
         members, offsets, nc = _clusters_arg(clusters)
-        summary, bp, ap, cnt = _Validation(), _vp(), _vp(), _u64()
-        st = _L.gg_validate_clusters(self._c, _ptr(sk), _ptr(ln), n, _ptr(members), _ptr(offsets), nc,
-                                     ctypes.c_float(ani), ctypes.byref(summary), ctypes.byref(bp), ctypes.byref(ap),
-                                     ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return _take_validation(summary, bp, ap, cnt)
+        summary, bad = _Validation(), _PairsOut()
+        self._call(_L.gg_validate_clusters, _ptr(sk), _ptr(ln), n, _ptr(members), _ptr(offsets), nc, _f32(ani),
+                   _byref(summary), *bad.refs)
+        return Validation(summary, *bad.take())
 
     def validate_files(self, paths, clusters, ani, cache_dir=None):
         """sketch_files(paths, cache_dir) followed by validate_clusters in one
         call (gg_validate_files): clusters index paths -> Validation."""
-        n = len(paths)
-        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        arr, n = _paths_arg(paths)
         members, offsets, nc = _clusters_arg(clusters)
-        summary, bp, ap, cnt = _Validation(), _vp(), _vp(), _u64()
-        st = _L.gg_validate_files(self._c, arr, n, _ptr(members), _ptr(offsets), nc, ctypes.c_float(ani),
-                                  None if cache_dir is None else os.fsencode(cache_dir), ctypes.byref(summary),
-                                  ctypes.byref(bp), ctypes.byref(ap), ctypes.byref(cnt))
-        if st != GG_OK:
-            raise self._err(st)
-        return _take_validation(summary, bp, ap, cnt)
+        summary, bad = _Validation(), _PairsOut()
+        self._call(_L.gg_validate_files, arr, n, _ptr(members), _ptr(offsets), nc, _f32(ani), _dir_arg(cache_dir),
+                   _byref(summary), *bad.refs)
+        return Validation(summary, *bad.take())
 
     def cluster_files(self, paths, min_ani, cluster_ani, cache_dir=None, want_pairs=True):
         """precluster_files(min_ani) followed by cluster_pairs(cluster_ani)
         in one call -> (rep_of, pairs, ani), or rep_of alone with
         want_pairs=False (the library then frees the pairs)."""
-        n = len(paths)
-        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        arr, n = _paths_arg(paths)
         rep_of = np.zeros(max(n, 1), np.uint32)
-        pp, ap, cnt = _vp(), _vp(), _u64()
-        st = _L.gg_cluster_files(self._c, arr, n, ctypes.c_float(min_ani), ctypes.c_float(cluster_ani),
-                                 None if cache_dir is None else os.fsencode(cache_dir), _ptr(rep_of),
-                                 ctypes.byref(pp) if want_pairs else None, ctypes.byref(ap) if want_pairs else None,
-                                 ctypes.byref(cnt) if want_pairs else None)
-        if st != GG_OK:
-            raise self._err(st)
+        out = _PairsOut()
+        self._call(_L.gg_cluster_files, arr, n, _f32(min_ani), _f32(cluster_ani), _dir_arg(cache_dir), _ptr(rep_of),
+                   *(out.refs if want_pairs else (None, None, None)))
         if not want_pairs:
             return rep_of[:n]
-        pairs, ani = self._pairs_ani(pp, ap, cnt.value)
+        pairs, ani = out.take()
         return rep_of[:n], pairs, ani
 
     def cluster_files_resident(self, paths, min_ani, cluster_ani, cache_dir=None):
@@ -1705,15 +1540,11 @@ class Context:
         a dict of n_pairs, ani_rechecked, n_preclusters, largest_precluster and
         pair_passes.  A multi-device context takes cluster_files' path and
         reports ani_rechecked and pair_passes as 0; the rest is the same."""
-        n = len(paths)
-        arr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
+        arr, n = _paths_arg(paths)
         rep_of = np.zeros(max(n, 1), np.uint32)
         summary = _ClusterSummary()
-        st = _L.gg_cluster_files_resident(self._c, arr, n, ctypes.c_float(min_ani), ctypes.c_float(cluster_ani),
-                                          None if cache_dir is None else os.fsencode(cache_dir), _ptr(rep_of),
-                                          ctypes.byref(summary))
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_cluster_files_resident, arr, n, _f32(min_ani), _f32(cluster_ani), _dir_arg(cache_dir),
+                   _ptr(rep_of), _byref(summary))
         return rep_of[:n], summary.as_dict()
 
     def precluster_files_each(self, paths, min_ani, each, cache_dir=None):
@@ -1722,8 +1553,8 @@ class Context:
         arrays of at most ~4M pairs (gg_precluster_files_each: galah's debug
         level, src/finch.rs:65-68, without holding every pair).  each returning
         True stops the call (GalahGpuError, status 9)."""
-        arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
-        pp, ap, cnt, hits = _vp(), _vp(), _u64(), _u32()
+        arr, n = _paths_arg(paths)
+        out, hits = _PairsOut(), _u32()
         raised = []
 
         def sink(_user, ptr, n):
@@ -1737,32 +1568,25 @@ class Context:
                 return 1
 
         cb = PAIR_SINK(sink)
-        st = _L.gg_precluster_files_each(self._c, arr, len(paths), ctypes.c_float(min_ani),
-                                         None if cache_dir is None else os.fsencode(cache_dir), cb, None,
-                                         ctypes.byref(pp), ctypes.byref(ap), ctypes.byref(cnt), ctypes.byref(hits))
-        self.last_cached = hits.value
+        st = _L.gg_precluster_files_each(self._c, arr, n, _f32(min_ani), _dir_arg(cache_dir), cb, None, *out.refs,
+                                         _byref(hits))
+        self.last_cached = hits.value  # (as precluster_files; then the callback's exception, then the status)
         if raised:
             raise raised[0]
         if st != GG_OK:
             raise self._err(st)
-        return self._pairs_ani(pp, ap, cnt.value)
+        return out.take()
 
     # -- device-resident API (torch tensors on this context's device) ---------
     def sketch_device(self, d_words, runs, n_genomes, d_out, d_lens, stream=None):
         rp, nr, runs = _runs_arg(runs)
-        st = _L.gg_sketch_device(self._c, _dev_ptr(d_words), d_words.numel(), rp, nr,
-                                 n_genomes, _dev_ptr(d_out), _dev_ptr(d_lens),
-                                 None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_sketch_device, _dev_ptr(d_words), d_words.numel(), rp, nr, n_genomes, _dev_ptr(d_out),
+                   _dev_ptr(d_lens), stream)
 
     def pairs_device(self, d_sketches, d_lens, n, tile_begin, tile_end, min_ani, d_out, out_cap, d_count,
                      stream=None):
-        st = _L.gg_pairs_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, tile_begin, tile_end,
-                                ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
-                                None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_pairs_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, tile_begin, tile_end, _f32(min_ani),
+                   _dev_ptr(d_out), out_cap, _dev_ptr(d_count), stream)
 
     def pairs_border_device(self, d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count, stream=None):
         """pairs_border over device-resident tensors, the contract of
@@ -1770,21 +1594,15 @@ class Context:
         number found, entries past out_cap dropped; asynchronous).  d_sketches
         may be a tensor with spare rows kept between updates: a batch of new
         sketches is written after the n_old rows it holds and only n grows."""
-        st = _L.gg_pairs_border_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, int(n_old),
-                                       ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
-                                       None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_pairs_border_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, int(n_old), _f32(min_ani),
+                   _dev_ptr(d_out), out_cap, _dev_ptr(d_count), stream)
 
     def cluster_pairs_device(self, n_genomes, d_pairs, d_ani, n_pairs, cluster_ani, d_rep_of, stream=None):
         """cluster_pairs over device-resident tensors: d_pairs n_pairs 16-byte
         gg_pair records, d_ani f32, d_rep_of u32 [n_genomes] (every entry is
         written).  Synchronises the stream; the input is not checked."""
-        st = _L.gg_cluster_pairs_device(self._c, n_genomes, _dev_ptr(d_pairs), _dev_ptr(d_ani), n_pairs,
-                                        ctypes.c_float(cluster_ani), _dev_ptr(d_rep_of),
-                                        None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_cluster_pairs_device, n_genomes, _dev_ptr(d_pairs), _dev_ptr(d_ani), n_pairs, _f32(cluster_ani),
+                   _dev_ptr(d_rep_of), stream)
 
     def ani_f32_device(self, d_pairs, n_pairs, d_ani, d_ani_f64=None, stream=None):
         """d_ani[p] = ani_f32(common, total, k) of the n_pairs 16-byte gg_pair
@@ -1792,11 +1610,8 @@ class Context:
         (optional) the f64 before rounding -> the number of entries the host
         recomputed.  Synchronises the stream."""
         cnt = _u64()
-        st = _L.gg_ani_f32_device(self._c, _dev_ptr(d_pairs), n_pairs, _dev_ptr(d_ani),
-                                  None if d_ani_f64 is None else _dev_ptr(d_ani_f64), ctypes.byref(cnt),
-                                  None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_f32_device, _dev_ptr(d_pairs), n_pairs, _dev_ptr(d_ani), _dev_opt(d_ani_f64), _byref(cnt),
+                   stream)
         return cnt.value
 
     def cluster_rows_device(self, d_sketches, d_lens, n, min_ani, cluster_ani, d_rep_of, want_summary=True,
@@ -1812,12 +1627,9 @@ class Context:
         Synchronises the stream."""
         summary = _ClusterSummary()
         pp, ap = _vp(), _vp()
-        st = _L.gg_cluster_rows_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, ctypes.c_float(min_ani),
-                                       ctypes.c_float(cluster_ani), _dev_ptr(d_rep_of),
-                                       ctypes.byref(summary) if want_summary else None,
-                                       ctypes.byref(pp), ctypes.byref(ap), None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_cluster_rows_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _f32(min_ani),
+                   _f32(cluster_ani), _dev_ptr(d_rep_of), _byref(summary) if want_summary else None, _byref(pp),
+                   _byref(ap), stream)
         if not want_summary:
             return None, pp.value or 0, ap.value or 0, None
         return summary.as_dict(), pp.value or 0, ap.value or 0, int(summary.n_pairs)
@@ -1832,13 +1644,8 @@ class Context:
         with an index >= n_genomes is left out, and d_pair_offsets[n_sets] is
         the number of local pairs written."""
         ns = _u32()
-        st = _L.gg_preclusters_device(self._c, n_genomes, _dev_ptr(d_pairs), n_pairs, _dev_ptr(d_members),
-                                      _dev_ptr(d_offsets), ctypes.byref(ns),
-                                      None if d_local is None else _dev_ptr(d_local),
-                                      None if d_pair_offsets is None else _dev_ptr(d_pair_offsets),
-                                      None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_preclusters_device, n_genomes, _dev_ptr(d_pairs), n_pairs, _dev_ptr(d_members),
+                   _dev_ptr(d_offsets), _byref(ns), _dev_opt(d_local), _dev_opt(d_pair_offsets), stream)
         return ns.value
 
     def ani_pairs_device(self, d_sketches, d_lens, n, d_list, m, stream=None):
@@ -1847,10 +1654,7 @@ class Context:
         are written in place (the integers only; ani_f32 gives the value).
         Asynchronous; the input is not checked: an entry with an index >= n
         receives 0 and 0."""
-        st = _L.gg_ani_pairs_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _dev_ptr(d_list), m,
-                                    None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_pairs_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _dev_ptr(d_list), m, stream)
 
     def pairs_matrix_device(self, d_sketches, d_lens, n, d_rows, m, min_ani, d_out, out_cap, d_count,
                             want_summary=True, stream=None):
@@ -1862,13 +1666,9 @@ class Context:
         position.  Synchronises the stream -> summary dict (None without
         want_summary; n_pairs may exceed out_cap)."""
         summary = _PairsMatrixSummary()
-        st = _L.gg_pairs_matrix_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n,
-                                       None if d_rows is None else _dev_ptr(d_rows), m, ctypes.c_float(min_ani),
-                                       _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
-                                       ctypes.byref(summary) if want_summary else None,
-                                       None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_pairs_matrix_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _dev_opt(d_rows), m,
+                   _f32(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
+                   _byref(summary) if want_summary else None, stream)
         return summary.as_dict() if want_summary else None
 
     def pairs_border_matrix_device(self, d_sketches, d_lens, n, n_old, min_ani, d_out, out_cap, d_count,
@@ -1880,12 +1680,9 @@ class Context:
         stream -> summary dict (None without want_summary; n_pairs may exceed
         out_cap)."""
         summary = _PairsMatrixSummary()
-        st = _L.gg_pairs_border_matrix_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, int(n_old),
-                                              ctypes.c_float(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
-                                              ctypes.byref(summary) if want_summary else None,
-                                              None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_pairs_border_matrix_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, int(n_old),
+                   _f32(min_ani), _dev_ptr(d_out), out_cap, _dev_ptr(d_count),
+                   _byref(summary) if want_summary else None, stream)
         return summary.as_dict() if want_summary else None
 
     def ani_matrix_device(self, d_sketches, d_lens, n, d_rows, m, d_common=None, d_total=None, d_ani=None,
@@ -1896,14 +1693,8 @@ class Context:
         each [m, m] or None, are written.  An index >= n is an empty row.
         Synchronises the stream -> summary dict."""
         summary = _MatrixSummary()
-        st = _L.gg_ani_matrix_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n,
-                                     None if d_rows is None else _dev_ptr(d_rows), m,
-                                     None if d_common is None else _dev_ptr(d_common),
-                                     None if d_total is None else _dev_ptr(d_total),
-                                     None if d_ani is None else _dev_ptr(d_ani), ctypes.byref(summary),
-                                     None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_matrix_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _dev_opt(d_rows), m,
+                   _dev_opt(d_common), _dev_opt(d_total), _dev_opt(d_ani), _byref(summary), stream)
         return summary.as_dict()
 
     def ani_matrix_groups_device(self, d_sketches, d_lens, n, d_members, offsets, d_common=None, d_total=None,
@@ -1915,14 +1706,9 @@ class Context:
         Synchronises the stream -> summary dict."""
         off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
         summary = _MatrixSummary()
-        st = _L.gg_ani_matrix_groups_device(self._c, _dev_ptr(d_sketches), _dev_ptr(d_lens), n,
-                                            None if d_members is None else _dev_ptr(d_members), _ptr(off), len(off) - 1,
-                                            None if d_common is None else _dev_ptr(d_common),
-                                            None if d_total is None else _dev_ptr(d_total),
-                                            None if d_ani is None else _dev_ptr(d_ani), ctypes.byref(summary),
-                                            None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_ani_matrix_groups_device, _dev_ptr(d_sketches), _dev_ptr(d_lens), n, _dev_opt(d_members),
+                   _ptr(off), len(off) - 1, _dev_opt(d_common), _dev_opt(d_total), _dev_opt(d_ani), _byref(summary),
+                   stream)
         return summary.as_dict()
 
     def synth_mixed_device(self, lens, cluster_size, max_sub_rate, n_run_rate, seed, d_words, stream=None,
@@ -1935,12 +1721,11 @@ class Context:
             runs = np.zeros(cap, dtype=RUN_DTYPE)
             nr = _u64()
             st = _L.gg_synth_mixed_device(self._c, first_genome, len(lens), _ptr(lens), cluster_size,
-                                          ctypes.c_float(max_sub_rate), ctypes.c_double(n_run_rate), seed,
-                                          _dev_ptr(d_words), _ptr(runs), cap, ctypes.byref(nr),
-                                          None if stream is None else stream)
+                                          _f32(max_sub_rate), _f64(n_run_rate), seed, _dev_ptr(d_words), _ptr(runs), cap,
+                                          _byref(nr), stream)
             if st == GG_OK:
                 return runs[:nr.value]
-            if st != 8:
+            if st != 8:  # (8: the run table was too small, nr holds the count: once more with that)
                 raise self._err(st)
             cap = nr.value
         raise self._err(st)
@@ -1948,11 +1733,8 @@ class Context:
     def synth_device(self, n_genomes, genome_len, cluster_size, max_sub_rate, seed, d_words, stream=None,
                      first_genome=0):
         runs = np.zeros(n_genomes, dtype=RUN_DTYPE)
-        st = _L.gg_synth_clustered_device(self._c, first_genome, n_genomes, genome_len, cluster_size,
-                                          ctypes.c_float(max_sub_rate), seed, _dev_ptr(d_words), _ptr(runs),
-                                          None if stream is None else stream)
-        if st != GG_OK:
-            raise self._err(st)
+        self._call(_L.gg_synth_clustered_device, first_genome, n_genomes, genome_len, cluster_size, _f32(max_sub_rate),
+                   seed, _dev_ptr(d_words), _ptr(runs), stream)
         return runs
 
 
@@ -2025,6 +1807,14 @@ class SortedPairGenomeDistanceCache:
 MISSING = object()
 
 
+def _cache_of(pairs, ani):
+    """The passing pairs and their f32 ANI as the cache finch::distances returns."""
+    cache = SortedPairGenomeDistanceCache()
+    for p, a in zip(pairs, ani):
+        cache.insert((int(p["i"]), int(p["j"])), np.float32(a))
+    return cache
+
+
 class PreclusterDistanceFinder:
     """src/lib.rs:23-27."""
 
@@ -2047,6 +1837,66 @@ def _context(k, s, seed=0):
         c = Context(k, s, seed, devices="all")
         _CTX_CACHE[key] = c
     return c
+
+
+@contextlib.contextmanager
+def _under_pairs_path(ctx, path):
+    """The body under pairs path `path` on a one-device context; the cached
+    context is shared, so what was set before is put back after it.  path
+    None, or a multi-device context: the body as it is."""
+    if path is None or ctx.device_count != 1:
+        yield
+        return
+    before = ctx.set_pairs_path(path)
+    try:
+        yield
+    finally:
+        ctx.set_pairs_path(before)
+
+
+@contextlib.contextmanager
+def _failing_as(what):
+    """A GalahGpuError of the body as the RuntimeError "<what>: <the error>" galah's flow reports."""
+    try:
+        yield
+    except GalahGpuError as e:
+        raise RuntimeError("%s: %s" % (what, e)) from e
+
+
+def _sketching():
+    return _failing_as("Failed to sketch genomes with finch")  # src/finch.rs:50
+
+
+def _clustering():
+    return _failing_as("Failed to cluster genomes")
+
+
+def _finch_only(who, preclusterer, clusterer):
+    """initialise() and the one combination that runs here: both methods "finch"."""
+    clusterer.initialise()
+    pre_name, clu_name = preclusterer.method_name(), clusterer.method_name()
+    if not (pre_name == clu_name == "finch"):
+        raise NotImplementedError("galah_amd.%s: only finch + finch runs here, not %s + %s" % (who, pre_name, clu_name))
+
+
+def _check_state(state, preclusterer):
+    """ValueError when the state was made with another k, sketch size, seed or min_ani."""
+    mine = (preclusterer.kmer_length, preclusterer.num_kmers, 0, np.float32(preclusterer.min_ani).tobytes())
+    if (state.k, state.s, state.seed, np.float32(state.min_ani).tobytes()) != mine:
+        raise ValueError("PreclusterState of k=%d s=%d seed=%d min_ani=%r, preclusterer of k=%d s=%d seed=0 "
+                         "min_ani=%r" % (state.k, state.s, state.seed, state.min_ani, preclusterer.kmer_length,
+                                         preclusterer.num_kmers, preclusterer.min_ani))
+
+
+def _new_paths(paths, present):
+    """The paths as strings; ValueError on one already present or given twice."""
+    new = [os.fspath(p) for p in paths]
+    seen = set(present)
+    for p in new:
+        if p in seen:
+            raise ValueError("genome already present: %s" % p)
+        seen.add(p)
+    return new
 
 
 def distances(genome_fasta_paths, min_ani, num_kmers, kmer_length, sketch_cache_dir=None, pairs_path=None):
@@ -2074,29 +1924,20 @@ def distances(genome_fasta_paths, min_ani, num_kmers, kmer_length, sketch_cache_
             log.debug("Comparing %s and %s, distance %s", paths[int(p["i"])], paths[int(p["j"])], rust_f64(d))
         return False
 
-    try:
+    with _sketching():
         ctx = _context(k, int(num_kmers))
         log.info("Sketching MinHash representations of each genome with finch ..")  # src/finch.rs:46
         thr = float(np.float32(min_ani))
         if every:
             pairs, ani = ctx.precluster_files_each(paths, thr, each, cache_dir=sketch_cache_dir)
         elif pairs_path is not None and ctx.device_count == 1:
-            before = ctx.set_pairs_path(pairs_path)  # (the cached context is shared: put back what was set)
-            try:
+            with _under_pairs_path(ctx, pairs_path):
                 pairs, ani, _ = ctx.precluster_files_resident(paths, thr, cache_dir=sketch_cache_dir)
-            finally:
-                ctx.set_pairs_path(before)
         else:
             pairs, ani = ctx.precluster_files(paths, thr, cache_dir=sketch_cache_dir)
-    except GalahGpuError as e:
-        # src/finch.rs:50
-        raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e
     log.info("Finished sketching genomes")  # src/finch.rs:48
     log.info(ctx.info_line())  # device count, phase times, fallbacks (gg_info_line)
-    cache = SortedPairGenomeDistanceCache()
-    for p, a in zip(pairs, ani):
-        cache.insert((int(p["i"]), int(p["j"])), np.float32(a))
-    return cache
+    return _cache_of(pairs, ani)
 
 
 def rust_f64(x):
@@ -2181,32 +2022,14 @@ class FinchPreclusterer(PreclusterDistanceFinder):
         involve a new genome are evaluated (Context.update_files).  ValueError
         when the state was made with another k, sketch size, seed or min_ani,
         or when a new path is already present."""
-        new_paths = [os.fspath(p) for p in new_paths]
-        mine = (self.kmer_length, self.num_kmers, 0, np.float32(self.min_ani).tobytes())
-        if (state.k, state.s, state.seed, np.float32(state.min_ani).tobytes()) != mine:
-            raise ValueError("PreclusterState of k=%d s=%d seed=%d min_ani=%r, preclusterer of k=%d s=%d seed=0 "
-                             "min_ani=%r" % (state.k, state.s, state.seed, state.min_ani, self.kmer_length,
-                                             self.num_kmers, self.min_ani))
-        seen = set(state.paths)
-        for p in new_paths:
-            if p in seen:
-                raise ValueError("genome already present: %s" % p)
-            seen.add(p)
-        try:
+        new_paths = [os.fspath(p) for p in new_paths]  # (first, as ever: a TypeError here comes before the state's ValueError)
+        _check_state(state, self)
+        new_paths = _new_paths(new_paths, state.paths)
+        with _sketching():
             ctx = _context(self.kmer_length, self.num_kmers)
-            if self.pairs_path is None or ctx.device_count != 1:
+            with _under_pairs_path(ctx, self.pairs_path):
                 sk, lens, border, border_ani = ctx.update_files(state.sketches, state.lens, new_paths,
                                                                 float(self.min_ani), cache_dir=self.sketch_cache_dir)
-            else:
-                before = ctx.set_pairs_path(self.pairs_path)  # (the cached context is shared: put back what was set)
-                try:
-                    sk, lens, border, border_ani = ctx.update_files(state.sketches, state.lens, new_paths,
-                                                                    float(self.min_ani),
-                                                                    cache_dir=self.sketch_cache_dir)
-                finally:
-                    ctx.set_pairs_path(before)
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
         pairs = np.concatenate([state.pairs, border])
         ani = np.concatenate([state.ani, border_ani])
         by_ij = np.lexsort((pairs["j"], pairs["i"]))  # SortedPairGenomeDistanceCache order
@@ -2232,10 +2055,7 @@ class PreclusterState:
 
     def cache(self):
         """The pairs as FinchPreclusterer.distances returns them."""
-        cache = SortedPairGenomeDistanceCache()
-        for p, a in zip(self.pairs, self.ani):
-            cache.insert((int(p["i"]), int(p["j"])), np.float32(a))
-        return cache
+        return _cache_of(self.pairs, self.ani)
 
     def save(self, file):
         """One .npz of plain arrays (no pickled objects): a path or a binary
@@ -2262,15 +2082,22 @@ class PreclusterState:
             return cls(paths, z["sketches"], z["lens"], pairs, z["ani"], k, s, seed, z["min_ani"][0])
 
 
+def _permutation(order, n=None):
+    """order as an int64 array; ValueError unless it is a permutation of 0 .. n-1 (n None: of its own length)."""
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    n = len(order) if n is None else n
+    if len(order) != n or (n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n)):
+        raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
+    return order
+
+
 def relabel_pairs(pairs, order):
     """The pairs of genomes numbered 0 .. n-1 renumbered by position in
     `order` (a permutation: position -> genome); i and j keep their places in
     each record, so a record may come out with i > j (cluster_pairs takes
     either orientation)."""
-    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    order = _permutation(order)
     n = len(order)
-    if n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n):
-        raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
     pos = np.empty(n, dtype=np.uint32)
     pos[order] = np.arange(n, dtype=np.uint32)
     out = np.array(pairs, dtype=PAIR_DTYPE).reshape(-1)
@@ -2290,19 +2117,13 @@ def cluster_update(state, new_paths, preclusterer, clusterer, order=None):
     that old representatives keep precedence.  clusters are lists of positions
     in that order, each with its representative first: what
     cluster([paths[g] for g in order], ...) returns."""
-    clusterer.initialise()
-    pre_name, clu_name = preclusterer.method_name(), clusterer.method_name()
-    if not (pre_name == clu_name == "finch"):
-        raise NotImplementedError("galah_amd.cluster_update: only finch + finch runs here, not %s + %s"
-                                  % (pre_name, clu_name))
+    _finch_only("cluster_update", preclusterer, clusterer)
     new_state = preclusterer.update(state, new_paths)
     n = len(new_state.paths)
     pairs = relabel_pairs(new_state.pairs, np.arange(n) if order is None else order)
-    try:
+    with _clustering():
         rep_of = _context(preclusterer.kmer_length, preclusterer.num_kmers).cluster_pairs(
             n, pairs, new_state.ani, float(np.float32(clusterer.get_ani_threshold())))
-    except GalahGpuError as e:
-        raise RuntimeError("Failed to cluster genomes: %s" % e) from e
     return clusters_from_reps(rep_of), new_state
 
 
@@ -2320,11 +2141,9 @@ class Collection:
         self._ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
         self._paths = list(_paths)
         self._h = None
-        try:
+        with _failing_as("Failed to make a collection"):
             self._h = _handle if _handle is not None else self._ctx.collection_create(
                 float(np.float32(preclusterer.min_ani)), reserve_rows=reserve, reserve_pairs=0)
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to make a collection: %s" % e) from e
 
     def close(self):
         if getattr(self, "_h", None):
@@ -2351,32 +2170,14 @@ class Collection:
     def info(self):
         return self._ctx.collection_stat(self._h)[0]
 
-    def _routed(self, call):
-        """call() under the preclusterer's pairs path, as FinchPreclusterer.update routes its border."""
-        ctx, path = self._ctx, self._pre.pairs_path
-        if path is None or ctx.device_count != 1:
-            return call()
-        before = ctx.set_pairs_path(path)  # (the cached context is shared: put back what was set)
-        try:
-            return call()
-        finally:
-            ctx.set_pairs_path(before)
-
     def add(self, paths):
         """Adds genomes (files) -> the number of pairs added.  ValueError on a
         path already present; a file that cannot be read or parsed leaves the
         collection as it was."""
-        new = [os.fspath(p) for p in paths]
-        seen = set(self._paths)
-        for p in new:
-            if p in seen:
-                raise ValueError("genome already present: %s" % p)
-            seen.add(p)
-        try:
-            added = self._routed(lambda: self._ctx.collection_add_files(self._h, new,
-                                                                        cache_dir=self._pre.sketch_cache_dir))
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
+        new = _new_paths(paths, self._paths)
+        # (under the preclusterer's pairs path, as FinchPreclusterer.update routes its border)
+        with _sketching(), _under_pairs_path(self._ctx, self._pre.pairs_path):
+            added = self._ctx.collection_add_files(self._h, new, cache_dir=self._pre.sketch_cache_dir)
         self._paths += new
         return added
 
@@ -2395,30 +2196,17 @@ class Collection:
 
     def cache(self):
         """The pairs as FinchPreclusterer.distances(self.paths) returns them."""
-        pairs, ani = self._ctx.collection_pairs(self._h)
-        cache = SortedPairGenomeDistanceCache()
-        for p, a in zip(pairs, ani):
-            cache.insert((int(p["i"]), int(p["j"])), np.float32(a))
-        return cache
+        return _cache_of(*self._ctx.collection_pairs(self._h))
 
     def cluster(self, clusterer, order=None):
         """The clusters of the collection's genomes as cluster_update returns
         them: lists of positions in `order` (position -> index into .paths;
         None: the paths' order), each with its representative first."""
-        clusterer.initialise()
-        pre_name, clu_name = self._pre.method_name(), clusterer.method_name()
-        if not (pre_name == clu_name == "finch"):
-            raise NotImplementedError("galah_amd.Collection.cluster: only finch + finch runs here, not %s + %s"
-                                      % (pre_name, clu_name))
+        _finch_only("Collection.cluster", self._pre, clusterer)
         if order is not None:
-            order = np.asarray(order, dtype=np.int64).reshape(-1)
-            n = len(self._paths)
-            if len(order) != n or (n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n)):
-                raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
-        try:
+            order = _permutation(order, len(self._paths))
+        with _clustering():
             rep_of = self._ctx.collection_cluster(self._h, float(np.float32(clusterer.get_ani_threshold())), order)
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to cluster genomes: %s" % e) from e
         return clusters_from_reps(rep_of)
 
     def query(self, paths, min_ani=None):
@@ -2429,10 +2217,8 @@ class Collection:
         itself at ANI 1.0).  The collection is not changed."""
         qp = [os.fspath(p) for p in paths]
         thr = float(np.float32(self._pre.min_ani if min_ani is None else min_ani))
-        try:
+        with _sketching():
             pairs, ani = self._ctx.collection_query_files(self._h, qp, thr, cache_dir=self._pre.sketch_cache_dir)
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
         n = len(self._paths)
         out = [[] for _ in qp]
         for p, a in zip(pairs, ani):
@@ -2447,32 +2233,22 @@ class Collection:
         decided alone: None when the genome would be a new representative,
         else (index into .paths of its representative, np.float32 ani).  The
         collection is not changed."""
-        clusterer.initialise()
-        pre_name, clu_name = self._pre.method_name(), clusterer.method_name()
-        if not (pre_name == clu_name == "finch"):
-            raise NotImplementedError("galah_amd.Collection.classify: only finch + finch runs here, not %s + %s"
-                                      % (pre_name, clu_name))
+        _finch_only("Collection.classify", self._pre, clusterer)
         n = len(self._paths)
         if order is not None:
-            order = np.asarray(order, dtype=np.int64).reshape(-1)
-            if len(order) != n or (n and (order.min() < 0 or order.max() >= n or len(np.unique(order)) != n)):
-                raise ValueError("order must be a permutation of 0 .. %d" % (n - 1))
+            order = _permutation(order, n)
         threshold = np.float32(clusterer.get_ani_threshold())
         qp = [os.fspath(p) for p in paths]
-        try:
+        with _clustering():
             rep_of = self._ctx.collection_cluster(self._h, float(threshold), order)
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to cluster genomes: %s" % e) from e
         # rank[row] = the representative's position in the order; other rows are no candidates
         rows = np.arange(n, dtype=np.int64) if order is None else order
         rank = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
         reps = np.nonzero(rep_of == np.arange(n, dtype=np.uint32))[0]
         rank[rows[reps]] = reps.astype(np.uint32)
-        try:
+        with _sketching():
             best, best_ani = self._ctx.collection_classify_files(self._h, qp, rank,
                                                                  cache_dir=self._pre.sketch_cache_dir)
-        except GalahGpuError as e:
-            raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
         return [None if int(b["i"]) == 0xFFFFFFFF or not np.float32(a) >= threshold else (int(b["i"]), np.float32(a))
                 for b, a in zip(best, best_ani)]
 
@@ -2488,11 +2264,7 @@ class Collection:
         """A collection holding a PreclusterState (gg_collection_load: the
         pairs are checked for form and trusted, not recomputed).  ValueError
         when the state was made with another k, sketch size, seed or min_ani."""
-        mine = (preclusterer.kmer_length, preclusterer.num_kmers, 0, np.float32(preclusterer.min_ani).tobytes())
-        if (state.k, state.s, state.seed, np.float32(state.min_ani).tobytes()) != mine:
-            raise ValueError("PreclusterState of k=%d s=%d seed=%d min_ani=%r, preclusterer of k=%d s=%d seed=0 "
-                             "min_ani=%r" % (state.k, state.s, state.seed, state.min_ani, preclusterer.kmer_length,
-                                             preclusterer.num_kmers, preclusterer.min_ani))
+        _check_state(state, preclusterer)
         ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
         try:
             h = ctx.collection_load(state.sketches, state.lens, state.pairs, state.ani,
@@ -2543,7 +2315,6 @@ class FinchClusterer(ClusterDistanceFinder):
         _, ani = _context(self.kmer_length, self.num_kmers).precluster_files([fasta1, fasta2], 0.0)
         return np.float32(ani[0]) if len(ani) else None
 
-
     def calculate_ani_many(self, pairs_of_paths, sketch_cache_dir=None):
         """calculate_ani for a list of (fasta1, fasta2): every distinct file
         sketched once (from sketch_cache_dir when it has it), then one
@@ -2581,30 +2352,21 @@ def cluster(genomes, preclusterer, clusterer, sketch_cache_dir=None):
     log.info("Preclustering and clustering methods are the same, so reusing ANI values")  # :31
     paths = list(genomes)
     cache_dir = sketch_cache_dir if sketch_cache_dir is not None else getattr(preclusterer, "sketch_cache_dir", None)
-    try:
+    with _sketching():
         ctx = _context(preclusterer.kmer_length, preclusterer.num_kmers)
         log.info("Sketching MinHash representations of each genome with finch ..")  # src/finch.rs:46
         min_ani, T = float(np.float32(preclusterer.min_ani)), float(np.float32(clusterer.get_ani_threshold()))
         if ctx.device_count == 1:
             # one device: the pair list stays in its memory, the preclusters'
             # count and largest size come back with rep_of
-            pairs_path = getattr(preclusterer, "pairs_path", None)
-            if pairs_path is None:
+            with _under_pairs_path(ctx, getattr(preclusterer, "pairs_path", None)):
                 rep_of, summary = ctx.cluster_files_resident(paths, min_ani, T, cache_dir=cache_dir)
-            else:
-                before = ctx.set_pairs_path(pairs_path)  # (the cached context is shared: put back what was set)
-                try:
-                    rep_of, summary = ctx.cluster_files_resident(paths, min_ani, T, cache_dir=cache_dir)
-                finally:
-                    ctx.set_pairs_path(before)
             n_sets, largest = summary["n_preclusters"], summary["largest_precluster"]
         else:
             rep_of, pairs, _ = ctx.cluster_files(paths, min_ani, T, cache_dir=cache_dir)
             if paths:
                 _, offsets = partition_preclusters(len(paths), pairs)
                 n_sets, largest = len(offsets) - 1, int(offsets[1] - offsets[0])
-    except GalahGpuError as e:
-        raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
     log.info("Finished sketching genomes")  # src/finch.rs:48
     log.info(ctx.info_line())
     log.info("Preclustering ..")  # :38
@@ -2711,12 +2473,10 @@ def validate_clusters(clustering_file, ani_threshold, num_kmers=1000, kmer_lengt
                 index[p] = len(genomes)
                 genomes.append(p)
     clusters = [[index[p] for p in c] for c in named]
-    try:
+    with _sketching():
         ctx = _context(int(kmer_length), int(num_kmers))
         sk, lens, n_cached = ctx.sketch_files(genomes, cache_dir=sketch_cache_dir)
         v = ctx.validate_clusters(sk, lens, clusters, float(thr))
-    except GalahGpuError as e:
-        raise RuntimeError("Failed to sketch genomes with finch: %s" % e) from e  # src/finch.rs:50
     out = ClusterValidation(v, clusters, genomes, n_cached)
     hundred = np.float32(100)
     if log.isEnabledFor(logging.DEBUG):
